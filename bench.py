@@ -8,7 +8,9 @@
 A "step" is one optimizer step of the comparison loop (train_files/trainchaos_comparison_1case.py:
 195-199): zero_grad, FuseUNet forward, CEMDiceLoss, backward, Adam(amsgrad) [+ gradient all-reduce],
 on a synthetic CHAOS-shaped batch (bs 4/GPU, 2 x 3 x 256 x 256, fp32) already resident in HBM.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: `value` images/s and `ms_per_step` over the K timed steps.  `--full` adds what the
+headline does not need (`roofline`, `kernels`, `streaming`, `cpu_baseline`, the N > 1 checks); `--dump-outputs DIR`
+writes what the last timed step computed.
 """
 import argparse
 import json
@@ -70,7 +72,48 @@ def parse():
                          'images/s, 32 -> 2.02, 64 -> 1.10, 128 -> 0.63, 256 -> 125 s per step)')
     ap.add_argument('--allow-probes', action='store_true',
                     help='run although AIDE_HIP_LIB selects another library build; the line is then marked INVALID (A-B tooling only)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: the dispatch-timed `roofline` / '
+                         '`kernels`, `roofline.critical` + `streaming`, live HBM traffic, `cpu_baseline`, and for N > 1 the '
+                         'exposed communication, first-contact record and replica check.  Without it a run sets up, warms up, '
+                         'times the K steps and prints the line; the options of those measurements (--no-cpu-baseline, '
+                         '--cpu-steps, --cpu-threads, --no-kernel-events, --event-steps, --traffic) act only with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (losses, logits, a fixed sample of the updated parameters '
+                         'and of their gradients, ...) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0)')
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.no_kernel_events, args.traffic = True, True, 'none'
+    return args
+
+
+DUMP_BYTES = 60 << 20                  # all arrays together, .npy headers aside: below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy, floating point as float32 (float64 and integer tensors
+    as float64).  An array larger than its equal share of DUMP_BYTES is replaced by a fixed sample of its flattened form: the
+    same seeded, sorted positions in every run and every build, so that two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:keep].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
+def net_state(net, suffix=''):
+    """the parameters after the optimizer step and their gradients, each flattened into one vector (for --dump-outputs)"""
+    ps = list(net.parameters())
+    return {'params' + suffix: torch.cat([p.detach().reshape(-1) for p in ps]),
+            'grads' + suffix: torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                         for p in ps])}
 
 
 KNOWN_SWITCHES = ('AIDE_HIP_LIB', 'AIDE_DIST_BACKEND', 'AIDE_PICK_STREAMS', 'AIDE_REPLAY', 'AIDE_DIRECT_GRADS', 'AIDE_ABI_COVERAGE')
@@ -163,8 +206,8 @@ def replica_check(nets, reducers, world, device):
                 replicas_identical=all(bool(torch.equal(a, allr[0])) for a in allr))
 
 
-def comm_block(world, reducers, per_rank, steps, check=None):
-    """N > 1: what was exchanged and what of it the step had to wait for."""
+def comm_block(world, reducers, per_rank, steps, check=None, full=False):
+    """N > 1: what was exchanged and (full) what of it the step had to wait for."""
     from aide_amd.distributed import comm_environment, first_contact
     if world == 1:
         return dict(backend=None, ranks=1, env=comm_environment())
@@ -179,7 +222,7 @@ def comm_block(world, reducers, per_rank, steps, check=None):
                 buckets=sum(d['buckets'] for d in desc), bytes_per_step=sum(d['bytes_per_step'] for d in desc),
                 env=comm_environment(), **(check or {}),
                 # link topology, RCCL's channel count, stream fallback (multi-GPU: first contact with real peers)
-                first_contact=first_contact() if dist.get_rank() == 0 else None,
+                first_contact=first_contact() if full and dist.get_rank() == 0 else None,
                 hw_queues=next((d['hw_queues'] for d in desc if d.get('hw_queues')), None),
                 exposed_ms=(round(sum(e for e in exposed if e is not None), 4)
                             if any(e is not None for e in exposed) else None),
@@ -428,7 +471,7 @@ def main_coteach(args, rank, world, device, batch, size, gflop_img, act, probes)
         broadcast_module(n1); broadcast_module(n2)
     reducers = [GradAllReduce(n1), GradAllReduce(n2)] if world > 1 else []      # installed on the engines
     for r in reducers:
-        r.time_exposed = True
+        r.time_exposed = args.full
     o1, o2 = Adam(n1.parameters(), lr=1e-4, amsgrad=True), Adam(n2.parameters(), lr=1e-4, amsgrad=True)
     op = CoTeachingProposedLoss(cediceweight=[1.0, 1.0], ceclassweight=[1.0, 1.0], segcor_weight=[1.0, 10.0])
     xin, xout, t = chaos_batch(batch, size, seed=1234 + rank)
@@ -445,7 +488,10 @@ def main_coteach(args, rank, world, device, batch, size, gflop_img, act, probes)
     timer = None if args.no_kernel_events else DispatchTimer(capacity=1200 * ev_steps)
     el, _, per_rank, r = timed_steps(step, args, world, device, timer, ev_steps)
     final = [round(float(r['loss1']), 6), round(float(r['loss2']), 6)]
-    check = replica_check([n1, n2], reducers, world, device)
+    if args.dump_outputs and rank == 0:
+        names = ('loss1', 'loss2', 'outputs1', 'outputs2', 'pl1', 'pl2', 'wm1', 'wm2', 'indx1', 'indx2')
+        dump_outputs(args.dump_outputs, dict({k: r[k] for k in names}, **net_state(n1, '1'), **net_state(n2, '2')))
+    check = replica_check([n1, n2], reducers, world, device) if args.full else None
     if timer is not None:
         timer.summary()                           # (read before queue_blocks re-arms the library's one timer)
     critical, streaming = queue_blocks(step, args, device, peak, el / args.steps * 1e3, world)
@@ -472,7 +518,7 @@ def main_coteach(args, rank, world, device, batch, size, gflop_img, act, probes)
                 step_tflops=round(value * gflop_img / 1e3, 2),
                 step_algorithmic_frac=round(value * gflop_img / 1e3 / world / peak, 4),
                 mfma_executed_frac=None if roof is None else roof['all_mfma_kernels']['executed_frac'],
-                final_loss=final, comm=comm_block(world, reducers, per_rank, args.steps, check), switches=act,
+                final_loss=final, comm=comm_block(world, reducers, per_rank, args.steps, check, args.full), switches=act,
                 roofline=roof, streaming=streaming, kernels=kernels, cpu_baseline=cpu)
     if probes:
         line['INVALID'] = 'non-default library build: %s' % ', '.join(probes)
@@ -506,10 +552,12 @@ def main():
         raise SystemExit('bench.py needs a HIP device (the product path has no CPU fallback)')
     if args.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be >= 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
     from aide_amd.distributed import init_from_env
-    rank, world, device = init_from_env(rccl_log=True)      # one process per GPU; RCCL group when WORLD_SIZE > 1
+    rank, world, device = init_from_env(rccl_log=args.full)     # one process per GPU; RCCL group when WORLD_SIZE > 1
     if world != args.gpus:
         raise SystemExit('bench.py: --gpus %d but WORLD_SIZE=%d' % (args.gpus, world))
     if world > 1:
@@ -538,7 +586,7 @@ def main():
         broadcast_module(net)
     reducers = [GradAllReduce(net)] if world > 1 else []
     for r in reducers:
-        r.time_exposed = True
+        r.time_exposed = args.full
     w = torch.tensor([1.0, 1.0])
     crit = U.CEMDiceLoss(cediceweight=w, ceclassweight=w, diceclassweight=w)
     opt = Adam(net.parameters(), lr=1e-4, amsgrad=True)
@@ -552,15 +600,17 @@ def main():
         loss = crit(out, tgt)
         loss.backward()
         opt.step()
-        return loss
+        return loss, out
 
     # every launch of every MFMA conv kernel in the timed steps carries a start / stop event pair holding the dispatch's
     # own begin / end timestamps (C ABI kernel timer): the steps keep their multi-stream schedule, nothing is serialised
     ev_steps = event_steps(args)
     timer = None if args.no_kernel_events else DispatchTimer(capacity=200 * ev_steps)
-    elapsed, _, per_rank, loss = timed_steps(step, args, world, device, timer, ev_steps)
+    elapsed, _, per_rank, (loss, logits) = timed_steps(step, args, world, device, timer, ev_steps)
     final_loss = float(loss.item())
-    check = replica_check([net], reducers, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(loss=loss, logits=logits, **net_state(net)))
+    check = replica_check([net], reducers, world, device) if args.full else None
     if timer is not None:
         timer.summary()                           # (read before queue_blocks re-arms the library's one timer)
     critical, streaming = queue_blocks(step, args, device, peak, elapsed / args.steps * 1e3, world)
@@ -595,7 +645,7 @@ def main():
                     # executed multiplies of ALL MFMA conv dispatches / their summed dispatch time / peak: utilisation
                     mfma_executed_frac=None if roof is None else roof['all_mfma_kernels']['executed_frac'],
                     final_loss=round(final_loss, 6),
-                    comm=comm_block(world, reducers, per_rank, args.steps, check), switches=act,
+                    comm=comm_block(world, reducers, per_rank, args.steps, check, args.full), switches=act,
                     roofline=roof, streaming=streaming, kernels=kernels, cpu_baseline=cpu)
         if probes:
             line['INVALID'] = 'non-default library build: %s' % ', '.join(probes)

@@ -232,6 +232,30 @@ def test_runtime_switch_inventory():
     assert len(bench.KNOWN_SWITCHES) <= 12
 
 
+def test_bench_dump_outputs_files_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host tensors: float32 / float64 .npy files; an array above its share of the byte budget
+    becomes an ordered sample of its elements, the same in every call; the budget keeps a dump under 64 MB"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_BYTES + 64 * 256 <= 64e6                   # (a header per file)
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    big = torch.randn(2000, generator=torch.Generator().manual_seed(3))
+    arrays = dict(big=big, small=torch.arange(6).reshape(2, 3), loss=torch.tensor(1.5, dtype=torch.float64),
+                  half=torch.tensor([0.25, -2.0], dtype=torch.bfloat16))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in arrays}
+    assert a['small'].dtype == np.float64 and a['small'].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert a['loss'].dtype == np.float64 and a['loss'].shape == () and float(a['loss']) == 1.5
+    assert a['half'].dtype == np.float32 and a['half'].tolist() == [0.25, -2.0]
+    assert a['big'].dtype == np.float32 and a['big'].shape == (4096 // 4 // 4,)
+    pos = [int(np.flatnonzero(big.numpy() == v)[0]) for v in a['big']]
+    assert pos == sorted(set(pos))
+    for n in arrays:
+        assert np.array_equal(np.load(str(tmp_path / 'b' / (n + '.npy'))), a[n])
+
+
 def test_wgrad_queue_is_caller_owned_host_state(built):
     """the batched slab reduce works on a caller-owned queue handle (no launches here: host state only); the library has
     no deferred-mode global any more"""

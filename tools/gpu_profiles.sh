@@ -8,15 +8,15 @@ cd $R
 if [ "$2" == "tests" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $O/${tag}_gputests.log 2>&1; tail -2 $O/${tag}_gputests.log
 fi
-python bench.py > $O/${tag}_bench_c2.json 2> $O/${tag}_bench_c2.err; tail -c 300 $O/${tag}_bench_c2.json
-python bench.py --workload c3 --steps 20 > $O/${tag}_bench_c3.json 2> $O/${tag}_bench_c3.err
-python bench.py --workload c4 > $O/${tag}_bench_c4.json 2> $O/${tag}_bench_c4.err
-python bench.py --workload c5 > $O/${tag}_bench_c5.json 2> $O/${tag}_bench_c5.err
+python bench.py --full > $O/${tag}_bench_c2.json 2> $O/${tag}_bench_c2.err; tail -c 300 $O/${tag}_bench_c2.json
+python bench.py --full --workload c3 --steps 20 > $O/${tag}_bench_c3.json 2> $O/${tag}_bench_c3.err
+python bench.py --full --workload c4 > $O/${tag}_bench_c4.json 2> $O/${tag}_bench_c4.err
+python bench.py --full --workload c5 > $O/${tag}_bench_c5.json 2> $O/${tag}_bench_c5.err
 for w in c3 c4 c5; do head -c 200 $O/${tag}_bench_$w.json; echo; done
 cd /tmp && export TMPDIR=/tmp
 for w in c2 c3 c4 c5; do
   st=""; [ $w == c3 ] && st="--steps 20"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof_$w -o $w -- python $R/bench.py --workload $w $st --no-cpu-baseline --traffic none > $O/${tag}_bench_${w}_under_rocprof.json 2> $O/${tag}_prof_$w.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof_$w -o $w -- python $R/bench.py --full --workload $w $st --no-cpu-baseline --traffic none > $O/${tag}_bench_${w}_under_rocprof.json 2> $O/${tag}_prof_$w.log
 done
 cd $R
 bash tools/pmc_mfma.sh $tag c2 > /dev/null 2>&1
