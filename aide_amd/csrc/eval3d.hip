@@ -1,0 +1,364 @@
+// Per-case evaluation on the device: the largest 3-D connected component of a label volume and the confusion sums of a
+// predicted volume against its target (include/aide_hip.h "per-case evaluation").
+//
+// Largest component: union-find over the logical raster index i = (i0 * D1 + i1) * D2 + i2 of the foreground voxels
+// (V != 0; face neighbours of EQUAL value are connected).  The root of a set is always its smallest index, so it IS the
+// component's first voxel in raster order.  Invariant: parent[i] <= i, and after the launch that initialises it every
+// global write to `parent` is an atomicMin -- parents only decrease, so every find and union loop ends, and no workgroup
+// ever waits for another (no spin, no co-residency assumption).  Launches:
+//   1 lcc_local   one workgroup per 4 x 16 x 16 tile: union-find in LDS; parent[i] = first voxel of i's blob inside the
+//                 tile (-1 for background), area[i] = that blob's voxel count at its first voxel, 0 elsewhere
+//   2 lcc_border  per tile, face-adjacent equal-valued pairs across its three lower faces joined with atomicMin; parent
+//                 words other workgroups write are read with agent-scope relaxed atomic loads (no stale L1 / L2 line)
+//   3 lcc_count   every tile-blob root that is no longer a root adds its area to its set's root (wave-aggregated atomics)
+//   4 lcc_select  key = (area << 32) | (0x7fffffff - root), block max, one atomicMax per block; flags whether any root
+//                 (hence any voxel) holds a positive value
+//   5 lcc_write   out[i] = 1 where find(i) is the chosen root (nothing when no voxel is positive: the reference's
+//                 `if mask.max() > 0`)
+// Everything is integer and the result does not depend on the schedule.
+#include "common.h"
+
+namespace {
+
+constexpr int TX = 16, TY = 16, TZ = 4, TILE = TX * TY * TZ;   // tile of logical (i0, i1, i2) = (z, y, x)
+
+struct Vol {
+    const long long* v;
+    long s0, s1, s2;   // element strides of the logical dims
+    int d0, d1, d2;
+    int tx, ty;        // tiles along i2, i1
+};
+
+__device__ __forceinline__ int ld_agent(const int* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x with path splitting: every node passed points on to its grandparent (atomicMin: only lowers, and the
+// grandparent is an ancestor in the same set)
+__device__ int find_split(int* parent, int x) {
+    int q = ld_agent(parent + x);
+    while (q != x) {
+        const int qq = ld_agent(parent + q);
+        if (qq != q) atomicMin(parent + x, qq);
+        x = q;
+        q = qq;
+    }
+    return x;
+}
+
+// join the sets of a and b: link the larger root under the smaller.  If the atomicMin finds that the larger root was
+// linked meanwhile (old != b), its old parent is carried on as b: the link it had is preserved through the next round
+__device__ void unite(int* parent, int a, int b) {
+    for (;;) {
+        a = find_split(parent, a);
+        b = find_split(parent, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(parent + b, a);
+        if (old == b) return;
+        b = old;
+    }
+}
+
+__device__ __forceinline__ int lds_find(volatile int* lp, int x) {
+    int q = lp[x];
+    while (q != x) { x = q; q = lp[x]; }
+    return x;
+}
+
+__device__ __forceinline__ void lds_unite(int* lp, int a, int b) {
+    volatile int* vp = lp;
+    for (;;) {
+        a = lds_find(vp, a);
+        b = lds_find(vp, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(lp + b, a);
+        if (old == b) return;
+        b = old;
+    }
+}
+
+__device__ __forceinline__ void tile_origin(const Vol& g, int tile, int& z0, int& y0, int& x0) {
+    const int tyx = g.tx * g.ty;
+    const int tz = tile / tyx, r = tile - tz * tyx, ty = r / g.tx;
+    z0 = tz * TZ; y0 = ty * TY; x0 = (r - ty * g.tx) * TX;
+}
+
+// thread t owns (y, x) = (t / 16, t % 16) of the tile at z = 0 .. 3: local index e = z * 256 + t
+__global__ __launch_bounds__(256) void lcc_local_kernel(Vol g, long tiles, int* __restrict__ parent,
+                                                        int* __restrict__ area, unsigned long long* __restrict__ ctrl) {
+    __shared__ long long val[TILE];
+    __shared__ int lp[TILE];
+    __shared__ int cnt[TILE];
+    const int t = threadIdx.x, y = t >> 4, x = t & 15;
+    const int plane = g.d1 * g.d2;
+    if (blockIdx.x == 0 && t == 0) { ctrl[0] = 0ull; ctrl[1] = 0ull; }
+    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        int z0, y0, x0;
+        tile_origin(g, (int)tile, z0, y0, x0);
+        const bool in_yx = y0 + y < g.d1 && x0 + x < g.d2;
+        __syncthreads();                          // the previous tile's LDS is read to the end
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = z * 256 + t;
+            long long v = 0;
+            if (in_yx && z0 + z < g.d0) v = g.v[(long)(z0 + z) * g.s0 + (long)(y0 + y) * g.s1 + (long)(x0 + x) * g.s2];
+            val[e] = v;
+            lp[e] = v != 0 ? e : -1;
+            cnt[e] = 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = z * 256 + t;
+            const long long v = val[e];
+            if (v == 0) continue;                 // (out-of-volume voxels read as background)
+            if (x > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
+            if (y > 0 && val[e - TX] == v) lds_unite(lp, e - TX, e);
+            if (z > 0 && val[e - TX * TY] == v) lds_unite(lp, e - TX * TY, e);
+        }
+        __syncthreads();
+        int root[TZ];
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = z * 256 + t;
+            root[z] = val[e] != 0 ? lds_find(lp, e) : -1;
+            if (root[z] >= 0) atomicAdd(&cnt[root[z]], 1);
+        }
+        __syncthreads();
+        if (!in_yx) continue;
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            if (z0 + z >= g.d0) break;
+            const int e = z * 256 + t;
+            const int gi = (z0 + z) * plane + (y0 + y) * g.d2 + x0 + x;
+            int gr = -1;
+            if (root[z] >= 0) {   // local order (z, y, x) is raster order: the tile-blob's first voxel has the lowest index
+                const int r = root[z], rz = r >> 8, ry = (r >> 4) & 15, rx = r & 15;
+                gr = (z0 + rz) * plane + (y0 + ry) * g.d2 + x0 + rx;
+            }
+            parent[gi] = gr;
+            area[gi] = cnt[e];
+        }
+    }
+}
+
+// the three lower faces of a tile: x face (TZ x TY pairs), y face (TZ x TX), z face (TY x TX)
+__global__ __launch_bounds__(256) void lcc_border_kernel(Vol g, long tiles, int* __restrict__ parent) {
+    const int plane = g.d1 * g.d2;
+    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        int z0, y0, x0;
+        tile_origin(g, (int)tile, z0, y0, x0);
+        for (int k = threadIdx.x; k < TZ * TY + TZ * TX + TY * TX; k += 256) {
+            int z, y, x, dz = 0, dy = 0, dx = 0;
+            if (k < TZ * TY) {
+                if (x0 == 0) continue;
+                z = k / TY; y = k % TY; x = 0; dx = 1;
+            } else if (k < TZ * TY + TZ * TX) {
+                if (y0 == 0) continue;
+                const int j = k - TZ * TY;
+                z = j / TX; x = j % TX; y = 0; dy = 1;
+            } else {
+                if (z0 == 0) continue;
+                const int j = k - TZ * TY - TZ * TX;
+                y = j / TX; x = j % TX; z = 0; dz = 1;
+            }
+            const int a0 = z0 + z, a1 = y0 + y, a2 = x0 + x;
+            if (a0 >= g.d0 || a1 >= g.d1 || a2 >= g.d2) continue;
+            const long off = (long)a0 * g.s0 + (long)a1 * g.s1 + (long)a2 * g.s2;
+            const long long v = g.v[off];
+            if (v == 0) continue;
+            const long long w = g.v[off - dz * g.s0 - dy * g.s1 - dx * g.s2];
+            if (w != v) continue;
+            const int gi = a0 * plane + a1 * g.d2 + a2;
+            unite(parent, gi - dz * plane - dy * g.d2 - dx, gi);
+        }
+    }
+}
+
+__device__ __forceinline__ int find_plain(const int* parent, int x) {
+    int q = parent[x];
+    while (q != x) { x = q; q = parent[x]; }
+    return x;
+}
+
+// tile-blob roots that were joined to another set add their area to its root.  Lanes of one wave that add to the same
+// root are summed first: one atomic per (wave, root)
+__global__ __launch_bounds__(256) void lcc_count_kernel(int* __restrict__ parent, int* __restrict__ area, int n) {
+    const int i = (int)min(blockIdx.x * 256u + threadIdx.x, (unsigned)n);
+    int a = 0, r = -1;
+    if (i < n) {
+        a = area[i];
+        if (a > 0) {
+            r = find_plain(parent, i);
+            if (r != i) atomicMin(parent + i, r);
+            else a = 0;
+        }
+    }
+    unsigned long long pending = __ballot(a > 0);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int rl = __shfl(r, leader);
+        const bool mine = a > 0 && r == rl;
+        int s = mine ? a : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(area + rl, s);
+        if (mine) a = 0;
+        pending &= ~__ballot(mine);
+    }
+}
+
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+// ctrl[0] = max key over the roots, ctrl[1] = 1 when some root (so some voxel) holds a positive value
+__global__ __launch_bounds__(256) void lcc_select_kernel(Vol g, const int* __restrict__ parent, const int* __restrict__ area,
+                                                         int n, unsigned long long* __restrict__ ctrl) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    unsigned long long key = 0;
+    int pos = 0;
+    const int plane = g.d1 * g.d2;
+    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
+        const int i = (int)u;
+        if (parent[i] != i) continue;
+        key = umax64(key, ((unsigned long long)(unsigned)area[i] << 32) | (unsigned)(0x7fffffff - i));
+        if (!pos) {
+            const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
+            pos = g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2] > 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        key = umax64(key, __shfl_xor(key, o));
+        pos |= __shfl_xor(pos, o);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { sk[wid] = key; sp[wid] = pos; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        key = umax64(umax64(sk[0], sk[1]), umax64(sk[2], sk[3]));
+        pos = sp[0] | sp[1] | sp[2] | sp[3];
+        if (key) atomicMax(ctrl, key);
+        if (pos) atomicMax(ctrl + 1, 1ull);
+    }
+}
+
+__global__ __launch_bounds__(256) void lcc_write_kernel(const int* __restrict__ parent, int n,
+                                                        const unsigned long long* __restrict__ ctrl,
+                                                        unsigned char* __restrict__ out) {
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (unsigned)n) return;
+    const int i = (int)u;
+    const unsigned long long key = ctrl[0];
+    const int best = ctrl[1] ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
+    const int p = parent[i];
+    out[i] = (best >= 0 && p >= 0 && find_plain(parent, p) == best) ? 1 : 0;
+}
+
+// ---- confusion sums: out[0..3] = N, sum P*T, sum P, sum T (int64, order-independent atomics) ----
+struct Operand {
+    const void* p;
+    long s0, s1, s2;
+};
+
+template <typename TP, typename TT>
+__global__ __launch_bounds__(256) void confusion_kernel(Operand P, Operand T, int d1, int d2, int n,
+                                                        long long* __restrict__ out) {
+    __shared__ long long sm[3][4];
+    const TP* pp = static_cast<const TP*>(P.p);
+    const TT* tp = static_cast<const TT*>(T.p);
+    const int plane = d1 * d2;
+    long long spt = 0, sp = 0, st = 0;
+    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
+        const int i = (int)u, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
+        const long long a = (long long)pp[(long)i0 * P.s0 + (long)i1 * P.s1 + (long)i2 * P.s2];
+        const long long b = (long long)tp[(long)i0 * T.s0 + (long)i1 * T.s1 + (long)i2 * T.s2];
+        spt += a * b; sp += a; st += b;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        spt += __shfl_xor(spt, o);
+        sp += __shfl_xor(sp, o);
+        st += __shfl_xor(st, o);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { sm[0][wid] = spt; sm[1][wid] = sp; sm[2][wid] = st; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const long long s = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+        atomicAdd(reinterpret_cast<unsigned long long*>(out + 1 + threadIdx.x), (unsigned long long)s);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 3) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)n);
+}
+
+bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
+    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
+    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
+    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t aide_lcc3d_ws_bytes(int64_t nvox) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    return (size_t)(2 * nvox) * sizeof(int) + 16 + 2 * sizeof(unsigned long long);
+}
+
+int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                           unsigned char* out, void* ws, hipStream_t stream) {
+    if (!dims_ok(d0, d1, d2)) return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    if (n == 0) return 0;
+    if (!v || !out || !ws) return AIDE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    int* parent = static_cast<int*>(ws);
+    int* area = parent + n;
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    Vol g;
+    g.v = v; g.s0 = (long)s0; g.s1 = (long)s1; g.s2 = (long)s2;
+    g.d0 = (int)d0; g.d1 = (int)d1; g.d2 = (int)d2;
+    g.tx = (int)((d2 + TX - 1) / TX); g.ty = (int)((d1 + TY - 1) / TY);
+    const long tiles = (long)g.tx * g.ty * ((d0 + TZ - 1) / TZ);
+    const unsigned nb = (unsigned)(((long)n + 255) / 256);
+    const unsigned ntile = (unsigned)min(tiles, 65536L);
+    const unsigned nsel = (unsigned)min((long)nb, 1024L);
+    const double bytes = 29.0 * n;   // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, select 4, write 4 + 1
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel, dim3(nb), dim3(256), 0, stream, parent, area, n);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_kernel, dim3(nsel), dim3(256), 0, stream, g,
+                      (const int*)parent, (const int*)area, n, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_write_kernel, dim3(nb), dim3(256), 0, stream, (const int*)parent, n,
+                      (const unsigned long long*)ctrl, out);
+    return aide_launch_status();
+}
+
+int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                        int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
+                        hipStream_t stream) {
+    if (!dims_ok(d0, d1, d2) || !out || (p_u8 != 0 && p_u8 != 1) || (t_u8 != 0 && t_u8 != 1)) return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    if (n > 0 && (!p || !t)) return AIDE_ERR_ARG;
+    hipError_t e = hipMemsetAsync(out, 0, 4 * sizeof(long long), stream);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return 0;
+    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2}, T{t, (long)t_s0, (long)t_s1, (long)t_s2};
+    const dim3 grid((unsigned)min(((long)n + 1023) / 1024, 1024L)), block(256);
+    const int e1 = (int)d1, e2 = (int)d2;
+    if (p_u8 && t_u8)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 2.0 * n, (confusion_kernel<unsigned char, unsigned char>), grid, block, 0, stream, P, T, e1, e2, n, out);
+    else if (p_u8)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 9.0 * n, (confusion_kernel<unsigned char, long long>), grid, block, 0, stream, P, T, e1, e2, n, out);
+    else if (t_u8)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 9.0 * n, (confusion_kernel<long long, unsigned char>), grid, block, 0, stream, P, T, e1, e2, n, out);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 16.0 * n, (confusion_kernel<long long, long long>), grid, block, 0, stream, P, T, e1, e2, n, out);
+    return aide_launch_status();
+}
+
+}  // extern "C"

@@ -4,11 +4,12 @@ Reference (train_files/trainchaos_comparison_1case.py:233-273, :275-314; the sam
 trainchaos_proposed_30cases1labeled.py:373-493 and evalchaos_comparison_1cases.py:143-243): for every
 slice of a case, bs=1: `argmax(softmax(net(inphase, outphase), dim=1), dim=1)` under `net.eval()` +
 `no_grad`, `.cpu().numpy()` per slice, `np.stack(..., axis=-1)`, then skimage's largest connected
-component (CPU, out of scope here) and `Dice3d_fn`.
+component and `Dice3d_fn` (the evaluation script: Dice, IoU, TP, TN, FP, FN).
 
 Here the slices of a case go through the eval-mode kernels in batches (eval BatchNorm uses the running
 statistics, so slices are independent and batching changes nothing but the launch count), the label
-map is one kernel (`aide_label_map`) and the volume leaves the device once.
+map is one kernel (`aide_label_map`), the largest-component filter and the confusion sums are kernels
+too (`aide_keep_largest_cc3d`, `aide_case_confusion`), and only what the caller asks for leaves the device.
 """
 import numpy as np
 import torch
@@ -53,8 +54,17 @@ def predict_labels(net, *modal_inputs, **kw):
 
 
 def predict_case(net, *modal_inputs, **kw):
-    """The reference's `generatedtarget`: numpy int64 [H,W,S] (slices stacked on the last axis, :267)."""
-    return predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0).contiguous().cpu().numpy()
+    """The reference's `generatedtarget`: numpy int64 [H,W,S] (slices stacked on the last axis, :267).
+    keep_largest=True: its largest connected component (:268), uint8, filtered on the device before anything leaves it.
+    numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered)."""
+    keep_largest = kw.pop('keep_largest', False)
+    as_numpy = kw.pop('numpy', True)
+    vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
+    if keep_largest:
+        vol = keep_largest_connected_components(vol)
+    if not as_numpy:
+        return vol
+    return vol.contiguous().cpu().numpy()
 
 
 def Dice3d_fn(inputs, targets):
@@ -76,6 +86,8 @@ def keep_largest_connected_components(mask):
     their first voxel; scipy.ndimage.label connects every non-zero voxel, so it is run once per label value and the blobs
     are ordered by their first voxel -- the same blob as the reference's `np.argmax(area)` on ties, and for a multi-class
     volume (num_classes up to 8 here) blobs of different classes stay separate as they do there."""
+    if isinstance(mask, torch.Tensor) and mask.is_cuda:
+        return _keep_largest_device(mask)
     from scipy import ndimage
     mask = np.asarray(mask)
     out = np.zeros(mask.shape, dtype=np.uint8)
@@ -97,3 +109,95 @@ def keep_largest_connected_components(mask):
                 best = (cand, blobs, b + 1)
     out[best[1] == best[2]] = 1
     return out
+
+
+_MAX_VOX = 2 ** 31 - 1
+_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8, torch.bool)
+
+
+def _lcc_args(mask):
+    """Argument checks of the device filter (before anything is launched): a 3-D integer tensor of < 2^31 voxels."""
+    if mask.dim() != 3:
+        raise RuntimeError('keep_largest_connected_components: a 3-D volume is expected, got %d dims' % mask.dim())
+    if mask.dtype not in _INT_DTYPES:
+        raise RuntimeError('keep_largest_connected_components: integer labels expected, got %s' % mask.dtype)
+    if mask.numel() > _MAX_VOX:
+        raise RuntimeError('keep_largest_connected_components: %d voxels, at most 2^31 - 1' % mask.numel())
+
+
+def _keep_largest_device(mask):
+    """HIP tensor (d0, d1, d2) of integer labels, any strides -> uint8 HIP tensor of the same shape (1 on the largest
+    blob); raster order is C order of the LOGICAL index.  Asynchronous: no host synchronisation."""
+    _lcc_args(mask)
+    mask = mask.detach()
+    if mask.dtype != torch.int64:
+        mask = mask.to(torch.int64)
+    out = torch.empty(mask.shape, device=mask.device, dtype=torch.uint8)
+    if mask.numel() == 0:
+        return out
+    ws = torch.empty(lib.aide_lcc3d_ws_bytes(mask.numel()), device=mask.device, dtype=torch.uint8)
+    check(lib.aide_keep_largest_cc3d(ptr(mask), *mask.shape, *mask.stride(), ptr(out), ptr(ws), stream_ptr()),
+          'keep_largest_cc3d')
+    return out
+
+
+def _confusion_args(pred, target):
+    """Argument checks of the device scores: integer volumes (int64 or uint8 here; other integer types are widened) of
+    the same shape, 1 to 3 dims (more are flattened into the first), < 2^31 voxels."""
+    if tuple(pred.shape) != tuple(target.shape):
+        raise RuntimeError('case_scores: shape mismatch %s vs %s' % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() == 0:
+        raise RuntimeError('case_scores: volumes of at least one dim expected')
+    for x in (pred, target):
+        if x.dtype not in _INT_DTYPES:
+            raise RuntimeError('case_scores: integer volumes expected, got %s' % x.dtype)
+    if pred.numel() > _MAX_VOX:
+        raise RuntimeError('case_scores: %d voxels, at most 2^31 - 1' % pred.numel())
+
+
+def _as3d(x):
+    x = x.detach()
+    if x.dtype not in (torch.int64, torch.uint8):
+        x = x.to(torch.int64)
+    if x.dim() > 3:
+        x = x.reshape((-1,) + tuple(x.shape[-2:]))
+    while x.dim() < 3:
+        x = x.unsqueeze(0)
+    return x
+
+
+def _confusion_device(pred, target):
+    """-> (N, sum P*T, sum P, sum T) as Python ints: one launch, one 32-byte device-to-host copy."""
+    _confusion_args(pred, target)
+    p, t = _as3d(pred), _as3d(target.to(pred.device))
+    out = torch.empty(4, device=p.device, dtype=torch.int64)
+    check(lib.aide_case_confusion(ptr(p), int(p.dtype == torch.uint8), *p.stride(), ptr(t), int(t.dtype == torch.uint8),
+                                  *t.stride(), *p.shape, ptr(out), stream_ptr()), 'case_confusion')
+    return tuple(int(v) for v in out.cpu().tolist())
+
+
+def _confusion_host(pred, target):
+    p = np.asarray(pred).reshape(-1).astype(np.int64)
+    t = np.asarray(target).reshape(-1).astype(np.int64)
+    if p.shape != t.shape:
+        raise RuntimeError('case_scores: shape mismatch %s vs %s' % (np.shape(pred), np.shape(target)))
+    return p.size, int(np.sum(p * t)), int(np.sum(p)), int(np.sum(t))
+
+
+def case_scores(pred, target):
+    """Per-case scores of the evaluation script (evalchaos_comparison_1cases.py:116-141, 238-242) for a predicted label
+    volume against its target: dict(Dice, IoU, TP, TN, FP, FN).  HIP tensors: one confusion launch and one copy of four
+    int64 sums to the host; anything else: the same sums in int64 on the CPU.  TP = sum p*t, FP = sum p - TP,
+    FN = sum t - TP, TN = N - sum p - sum t + TP (the reference's formulas, exact for any integers); Dice = 2 TP /
+    (sum p + sum t) and IoU = TP / (sum p + sum t - TP) as float64 true division like numpy's (0/0 -> nan, x/0 -> inf)."""
+    dev = [x for x in (pred, target) if isinstance(x, torch.Tensor) and x.is_cuda]
+    if dev:
+        pred = torch.as_tensor(pred, device=dev[0].device)
+        target = torch.as_tensor(target, device=dev[0].device)
+        n, spt, sp, st = _confusion_device(pred, target)
+    else:
+        n, spt, sp, st = _confusion_host(pred, target)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        dice = np.float64(2 * spt) / np.float64(sp + st)
+        iou = np.float64(spt) / np.float64(sp + st - spt)
+    return dict(Dice=dice, IoU=iou, TP=spt, TN=n - sp - st + spt, FP=sp - spt, FN=st - spt)

@@ -134,18 +134,21 @@ def Train(args=None):
 
 
 def evaluate_case(net, args, device, single, epoch, slices=8):
-    """3-D Dice of one synthetic case predicted slice-batch-wise in eval mode (aide_amd.inference.predict_case)."""
-    from aide_amd.inference import predict_case, Dice3d_fn, keep_largest_connected_components
+    """3-D Dice of one synthetic case predicted slice-batch-wise in eval mode (aide_amd.inference.predict_case), with the
+    largest-component filter and the sums of the Dice on the device: one copy of four int64 sums leaves it."""
+    from aide_amd.inference import predict_case, case_scores
     from aide_amd.synthetic import chaos_batch
     inphase, outphase, targets = chaos_batch(slices, args.img_size, seed=args.torch_seed * 7919 + 13, single_modal=single)
     net.eval()
-    pred = predict_case(net, inphase, batch_size=slices) if single else predict_case(net, inphase, outphase, batch_size=slices)
+    mods = (inphase,) if single else (inphase, outphase)
+    # :267: keep_largest_connected_components of the [H,W,S] label volume (on the device here)
+    pred = predict_case(net, *mods, batch_size=slices, keep_largest=True, numpy=False)
     net.train()
-    pred = keep_largest_connected_components(pred)                   # :267-268 (CPU post-processing, as in the reference)
-    tgt = targets.permute(1, 2, 0).contiguous().numpy()
-    if tgt.sum() == 0 and pred.sum() == 0:
+    tgt = targets.to(device).permute(1, 2, 0)
+    s = case_scores(pred, tgt)                                         # :268: Dice3d_fn = s["Dice"]
+    if s['TP'] + s['FN'] == 0 and s['TP'] + s['FP'] == 0:             # tgt.sum() == 0 and pred.sum() == 0
         return 1.0
-    return float(Dice3d_fn(pred, tgt))
+    return float(s['Dice'])
 
 
 if __name__ == '__main__':

@@ -542,6 +542,26 @@ int aide_pixelcoreg_bwd(const float* z1, const float* z2, const float* z3, const
  * for two classes, int64 like torch.argmax; ties (also those created by the softmax rounding) -> 0 */
 int aide_label_map(const float* logits, int64_t l_bs, int N, int HW, long long* labels, aide_stream_t stream);
 
+/* ---- per-case evaluation: largest 3-D connected component, confusion sums ----------------------
+ * replaces the CPU post-processing of the per-case loop: keep_largest_connected_components (skimage
+ * measure.label(connectivity=1) + regionprops + argmax(area), trainchaos_comparison_1case.py:67-77, called at
+ * :267-268; trainchaos_proposed_30cases1labeled.py:103-112; evalchaos_comparison_1cases.py:232) and the scores
+ * Dice3d_fn / IoU3d_fn / TP_TN_FP_FN3d (evalchaos_comparison_1cases.py:116-141, 238-242).
+ * Volumes have a LOGICAL shape (d0, d1, d2) and element strides (s0, s1, s2): raster order is C order of the logical
+ * index, so [S,H,W] labels passed as a permute(1, 2, 0) view are scanned in the reference's [H,W,S] order. */
+/* workspace of aide_keep_largest_cc3d for nvox = d0 * d1 * d2 voxels (16-byte aligned); 0 for nvox >= 2^31 */
+size_t aide_lcc3d_ws_bytes(int64_t nvox);
+/* out[d0][d1][d2] (uint8, contiguous) = 1 on the largest blob of v, 0 elsewhere.  Foreground: v != 0; face neighbours
+ * holding the SAME value are connected; ties in voxel count go to the blob whose first voxel comes first in raster
+ * order; all zeros when the volume has no positive value.  d0 * d1 * d2 < 2^31 (AIDE_ERR_ARG otherwise). */
+int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                           unsigned char* out, void* ws, aide_stream_t stream);
+/* out[4] (int64) = {N, sum p*t, sum p, sum t} over the logical volume; p / t are int64 (x_u8 = 0) or uint8 (x_u8 = 1)
+ * with element strides.  TP = out[1], FP = out[2] - out[1], FN = out[3] - out[1], TN = N - out[2] - out[3] + out[1] */
+int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                        int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
+                        aide_stream_t stream);
+
 /* ---- Adam(amsgrad), one launch for all parameter tensors ----------------------------------------
  * replaces torch.optim.Adam(net.parameters(), lr, amsgrad=True): trainchaos_comparison_1case.py:170 */
 int aide_adam_amsgrad_multi(float* const* p, const float* const* g, float* const* m, float* const* v,
