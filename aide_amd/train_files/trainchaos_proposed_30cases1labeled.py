@@ -54,6 +54,26 @@ def parse_args(argv=None):
 TWO_NET_STREAMS = [True]
 _NET2_STREAM = {}
 
+# Train() builds the augmented views of a step the way the reference's loader does -- Resize, RandomRotate, RandomHorizontallyFlip,
+# ToTensor, Normalize of datasetchaos_proposed/transform.py, from the u8 slices of the synthetic batch, with --rotation and
+# --data_mean / --data_std -- on the device (utils/loader_aug.py), so that the pseudo labels ensemble views that were rotated and
+# flipped by the angles reverseaug undoes.  Off: the scaled copies of the inputs (the measured default path).
+DEVICE_AUGMENT = [False]
+
+
+def _device_views(aug, rng, n, size, seed, single, device):
+    """one synthetic batch (the slices chaos_batch draws for `seed`) through LoaderAugment -> (inphase, outphase or None,
+    targets, augmented inputs, augset)"""
+    from aide_amd.synthetic import chaos_slice
+    from aide_amd.utils.loader_aug import draw_aug_params
+    r = np.random.RandomState(seed)
+    sl = [chaos_slice(r, size) for _ in range(n)]
+    base, augset, _ = aug([s[0] if single else (s[0], s[1]) for s in sl], draw_aug_params(n, aug.rotation, rng), device=device)
+    t = torch.from_numpy(np.stack([s[2] for s in sl])).pin_memory().to(device, non_blocking=True)
+    if single:
+        return base[0], None, t, [augset['img%d' % k] for k in range(1, 5)], augset
+    return base[0], base[1], t, [(augset['imgmodal1%d' % k], augset['imgmodal2%d' % k]) for k in range(1, 5)], augset
+
 
 def _net2_stream(device):
     s = _NET2_STREAM.get(device)
@@ -242,6 +262,11 @@ def Train(args=None, variant='chaos'):
     sch2 = make_scheduler(args.lr_policy, opt2, args.num_epoch)
     g = torch.Generator(device='cpu').manual_seed(args.torch_seed)
     single = not var['two_modal']
+    if DEVICE_AUGMENT[0]:
+        from aide_amd.utils.loader_aug import LoaderAugment
+        loader_aug = LoaderAugment(args.img_size, getattr(args, 'rotation', 60.0), getattr(args, 'data_mean', None),
+                                   getattr(args, 'data_std', None))
+        aug_rng = random.Random(args.torch_seed)
     best = 0.0                                                        # :244
     for epoch in range(args.num_epoch):
         ts = time.time()
@@ -251,22 +276,26 @@ def Train(args=None, variant='chaos'):
         l1 = torch.zeros((), device=device)
         l2 = torch.zeros((), device=device)
         for it in range(args.steps_per_epoch):
-            xin, xout, t = chaos_batch(args.batch_size, args.img_size,
-                                       seed=(args.torch_seed * 100003 + epoch * 1009 + it) * world + rank)
-            if single:
-                augs = [(xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device) for _ in range(4)]
-                xin, xout, t = xin.to(device), None, t.to(device)
+            seed = (args.torch_seed * 100003 + epoch * 1009 + it) * world + rank
+            if DEVICE_AUGMENT[0]:
+                xin, xout, t, augs, augset = _device_views(loader_aug, aug_rng, args.batch_size, args.img_size, seed, single,
+                                                           device)
             else:
-                augs = [((xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device),
-                         (xout * (1 + 0.1 * torch.randn(1, generator=g))).to(device)) for _ in range(4)]
-                xin, xout, t = xin.to(device), xout.to(device), t.to(device)
-            # augmentation bookkeeping as the loader's dict (:81-95): 4 augmentations per sample, random flips and rotations
-            # within +-args.rotation; the logits are mapped back on the device (aide_reverse_aug)
-            augset = {'augno': [4] * args.batch_size}
-            for k in range(4):
-                augset['hflip%d' % (k + 1)] = [int(torch.randint(0, 2, (1,), generator=g)) for _ in range(args.batch_size)]
-                augset['degree%d' % (k + 1)] = [float((torch.rand(1, generator=g) * 2 - 1) * args.rotation)
-                                                for _ in range(args.batch_size)]
+                xin, xout, t = chaos_batch(args.batch_size, args.img_size, seed=seed)
+                if single:
+                    augs = [(xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device) for _ in range(4)]
+                    xin, xout, t = xin.to(device), None, t.to(device)
+                else:
+                    augs = [((xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device),
+                             (xout * (1 + 0.1 * torch.randn(1, generator=g))).to(device)) for _ in range(4)]
+                    xin, xout, t = xin.to(device), xout.to(device), t.to(device)
+                # augmentation bookkeeping as the loader's dict (:81-95): 4 augmentations per sample, random flips and rotations
+                # within +-args.rotation; the logits are mapped back on the device (aide_reverse_aug)
+                augset = {'augno': [4] * args.batch_size}
+                for k in range(4):
+                    augset['hflip%d' % (k + 1)] = [int(torch.randint(0, 2, (1,), generator=g)) for _ in range(args.batch_size)]
+                    augset['degree%d' % (k + 1)] = [float((torch.rand(1, generator=g) * 2 - 1) * args.rotation)
+                                                    for _ in range(args.batch_size)]
             r = coteach_step(net1, net2, opt1, opt2, loss_op, xin, xout, augs, t, t, rate, args.temperature, augset=augset,
                              pipeline=True, eval_aug=var['eval_aug'], sharpen=var['sharpen'])
             l1 += r['loss1']

@@ -6,5 +6,6 @@ from .coteach_loss import (Coteachingloss_dropimage, Coteachingloss_weightimage,
                            Coteachingloss_dropimagedroppixel, KLbidirection, CoTeachingProposedLoss,
                            pseudo_label_ensemble)
 from .augment import reverseaug, reverse_aug_tensor  # noqa: F401
+from .loader_aug import LoaderAugment, draw_aug_params, CHAOS_PALETTE  # noqa: F401
 from .reg_loss import Pixelcoreg_Focalloss, Pixelcoreg_Focalloss_twomodel  # noqa: F401
 from .poly_lr_scheduler import PolyLR  # noqa: F401

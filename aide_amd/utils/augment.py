@@ -67,6 +67,13 @@ def reverseaug(augset, augoutput, classno):
     if naug == 0:
         return augoutput
     h, w = augoutput[0].shape[2], augoutput[0].shape[3]
+    cached = augset.get('_aide_revpar')              # rows LoaderAugment uploaded with its views (utils/loader_aug.py)
+    if cached is not None and cached[1] == (h, w) and tuple(cached[0].shape[:2]) == (naug, nb) and \
+            all(int(a) == naug for a in augset['augno']):
+        for k in range(naug):
+            assert augoutput[k].shape[1] == classno
+            augoutput[k] = reverse_aug_tensor(augoutput[k].contiguous(), None, None, par=cached[0][k])
+        return augoutput
     rows = []
     for k in range(naug):
         assert augoutput[k].shape[1] == classno

@@ -562,6 +562,24 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
                         int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
                         aide_stream_t stream);
 
+/* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
+ * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
+ * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
+ * The tables come from aide_amd/utils/loader_aug.py: src = packed u8 / u16 planes; desc[p] = 8 ints {byte offset, h, w,
+ * u16, x table, y table, kx, ky} (table offsets in ints into tab; an entry per output index {first tap, taps, kx / ky 22-bit
+ * weights}) for the N * M source planes p = n * M + m; par[n][k] = {PIL inverse affine a..f, hflip, mode} of augmentation k
+ * (mode 1 / 2 / 3 / 4: the 0 / 180 / 90 / 270 degree transpose paths); norm = {mean[3], std[3]} or NULL (per-image mean and
+ * unbiased std of the resized base).  out[m][v][n]: v = 0 the base image, v = k the view of augmentation k, each [3][S][S]
+ * float32, or [S][S] u8 with out_u8 (16-byte aligned when float).  ws: aide_loader_aug_ws_bytes(N * M, S), 16-byte aligned.
+ * Two launches; augno 0 .. 4. */
+size_t aide_loader_aug_ws_bytes(int nplanes, int S);
+int aide_loader_aug(const void* src, const int* desc, const int* tab, const double* par, const float* norm, int N, int M,
+                    int S, int augno, int out_u8, void* out, void* ws, aide_stream_t stream);
+/* out[q] = [npal][S][S] int64 one-hot of mask plane q (u8) resized NEAREST; desc[q] = 8 ints {byte offset, h, w, 0, x index
+ * table, y index table, 0, 0}; a value outside the palette (1 .. 8 entries, device ints) gives an all-zero row.  One launch. */
+int aide_loader_mask_onehot(const void* src, const int* desc, const int* tab, const int* palette, int nplanes, int S,
+                            int npal, long long* out, aide_stream_t stream);
+
 /* ---- Adam(amsgrad), one launch for all parameter tensors ----------------------------------------
  * replaces torch.optim.Adam(net.parameters(), lr, amsgrad=True): trainchaos_comparison_1case.py:170 */
 int aide_adam_amsgrad_multi(float* const* p, const float* const* g, float* const* m, float* const* v,
