@@ -4,8 +4,8 @@ Replaces torch.optim.Adam(net.parameters(), lr=args.lr, amsgrad=True)
 (train_files/trainchaos_comparison_1case.py:170; two instances in
 trainchaos_proposed_30cases1labeled.py:231-232). Same constructor arguments, param_groups layout and
 state keys ('step', 'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq') as torch.optim.Adam, so LR schedulers
-(StepLR(30, 0.5), :173-176) and state_dict round-trips keep working.  HBM-bound: 20 B/param read,
-16 B/param written (amsgrad)."""
+(StepLR(30, 0.5), :173-176) and state_dict round-trips keep working.  Step counts are per parameter, as in torch.
+HBM-bound: 20 B/param read, 16 B/param written (amsgrad)."""
 import ctypes
 
 import torch
@@ -44,6 +44,8 @@ class Adam(torch.optim.Optimizer):
                 p.grad = None
 
     def _launch(self, tab, gtab, n, group, step):
+        if tab['total_blocks'] == 0:               # every tensor empty: nothing to update (the kernel rejects an empty grid)
+            return
         b1, b2 = group['betas']
         check(lib.aide_adam_amsgrad_multi(ptr(tab['p']), ptr(gtab), ptr(tab['m']), ptr(tab['v']),
                                           ptr(tab['vmax']), ptr(tab['sizes']), ptr(tab['starts']),
@@ -51,13 +53,13 @@ class Adam(torch.optim.Optimizer):
                                           float(b2), float(group['eps']), float(group['weight_decay']),
                                           int(bool(group['amsgrad'])), step, stream_ptr()), 'adam')
 
-    def _static_table(self, gi, plist):
+    def _static_table(self, slot, plist):
         # the table holds raw pointers to the parameters AND their moment tensors: load_state_dict (or any replacement
         # of a state tensor) must invalidate it
-        key = tuple(p.data_ptr() for p in plist) + tuple(
-            t.data_ptr() for p in plist for t in (self.state[p]['exp_avg'], self.state[p]['exp_avg_sq'],
-                                                  self.state[p].get('max_exp_avg_sq')) if t is not None)
-        tab = self._tables.get(gi)
+        st = [self.state[p] for p in plist]
+        key = tuple((p.data_ptr(), p.numel(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr(),
+                     s['max_exp_avg_sq'].data_ptr() if 'max_exp_avg_sq' in s else 0) for p, s in zip(plist, st))
+        tab = self._tables.get(slot)
         if tab is not None and tab['key'] == key:
             return tab
         dev = plist[0].device
@@ -66,18 +68,37 @@ class Adam(torch.optim.Optimizer):
         for s in sizes:
             starts.append(acc)
             acc += (s + 1023) // 1024
-        st = [self.state[p] for p in plist]
 
         def table(vals):
             return torch.tensor(vals, dtype=torch.int64).to(dev)
         tab = dict(key=key, total_blocks=acc,
-                   p=table([p.data_ptr() for p in plist]),
-                   m=table([s['exp_avg'].data_ptr() for s in st]),
-                   v=table([s['exp_avg_sq'].data_ptr() for s in st]),
-                   vmax=table([s['max_exp_avg_sq'].data_ptr() if 'max_exp_avg_sq' in s else 0 for s in st]),
-                   sizes=table(sizes), starts=table(starts))
-        self._tables[gi] = tab
+                   p=table([k[0] for k in key]), m=table([k[2] for k in key]), v=table([k[3] for k in key]),
+                   vmax=table([k[4] for k in key]), sizes=table(sizes), starts=table(starts))
+        self._tables[slot] = tab
         return tab
+
+    def _grad_table(self, slot, grads):
+        # the gradient pointer table only changes when the gradients move (the engine's arena usually comes back at the
+        # same address every step): rebuild + upload it only then
+        gkey = tuple(g.data_ptr() for g in grads)
+        cached = self._gtabs.get(slot)
+        if cached is not None and cached[0] == gkey:
+            return gkey, cached[1]
+        gtab = torch.tensor(gkey, dtype=torch.int64).to(grads[0].device, non_blocking=True)
+        self._gtabs[slot] = (gkey, gtab)
+        return gkey, gtab
+
+    @staticmethod
+    def _state_unchanged(fast):
+        # the caller may replace a moment tensor or set a step count between steps (state[p]['exp_avg'] = ...,
+        # state[p]['step'] = 0): the cached pointer table and step no longer describe the state.  Identity tests only;
+        # every step count is the very int object the last step stored
+        step = fast['step']
+        for st, m, v, vm in fast['moments']:
+            if st['step'] is not step or st['exp_avg'] is not m or st['exp_avg_sq'] is not v or \
+                    st.get('max_exp_avg_sq') is not vm:
+                return False
+        return True
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -85,9 +106,10 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        keep = []
         for gi, group in enumerate(self.param_groups):
-            # steady state: same parameters, same moment tensors, every gradient present and where it was last step (the
-            # engine's arena views) -- nothing to validate or rebuild, one launch
+            # steady state: same parameters, same state, every gradient present and where it was last step (the engine's
+            # arena views) -- nothing to validate or rebuild, one launch
             fast = self._fast.get(gi)
             if fast is not None:
                 params = group['params']
@@ -95,12 +117,12 @@ class Adam(torch.optim.Optimizer):
                 if fast['params'] is params and len(params) == fast['n'] and all(g is not None for g in grads) and \
                         tuple(g.data_ptr() for g in grads) == fast['gkey'] and \
                         tuple(p.data_ptr() for p in params) == fast['pkey'] and \
-                        bool(group['amsgrad']) == fast['amsgrad']:
+                        bool(group['amsgrad']) == fast['amsgrad'] and self._state_unchanged(fast):
                     step = fast['step'] = fast['step'] + 1
                     for st in fast['states']:
                         st['step'] = step
                     self._launch(fast['tab'], fast['gtab'], fast['n'], group, step)
-                    self._keep = (fast['gtab'], None)
+                    keep.append(fast['gtab'])
                     continue
                 self._fast.pop(gi, None)
             plist = [p for p in group['params'] if p.grad is not None]
@@ -118,36 +140,37 @@ class Adam(torch.optim.Optimizer):
                     st['exp_avg_sq'] = torch.zeros_like(p)
                     if group['amsgrad']:
                         st['max_exp_avg_sq'] = torch.zeros_like(p)
-            if len(plist) != len(group['params']):
-                self._tables.pop(gi, None)        # membership changed: rebuild
-            tab = self._static_table(gi, plist)
-            grads = []
+            # torch.optim.Adam counts steps per parameter: one that missed steps (frozen, or no gradient) has its own bias
+            # corrections.  One launch per distinct count -- a single one unless the group's parameters disagree.  A
+            # torch.optim.Adam checkpoint stores 'step' as a (float) tensor: coerce
+            buckets = {}
             for p in plist:
-                g = p.grad
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                grads.append(g)
-            # the gradient pointer table only changes when the gradients move (the engine's arena usually comes back at
-            # the same address every step): rebuild + upload it only then
-            gkey = tuple(g.data_ptr() for g in grads)
-            cached = self._gtabs.get(gi)
-            if cached is not None and cached[0] == gkey:
-                gtab = cached[1]
-            else:
-                gtab = torch.tensor(gkey, dtype=torch.int64).to(plist[0].device, non_blocking=True)
-                self._gtabs[gi] = (gkey, gtab)
-            # a torch.optim.Adam checkpoint stores 'step' as a (float) tensor: coerce
-            step = int(self.state[plist[0]]['step']) + 1
-            for p in plist:
-                self.state[p]['step'] = step
-            self._launch(tab, gtab, len(plist), group, step)
-            # keep alive until the next step (async launch): the pointer table and the contiguous COPIES made above -- not
-            # the parameters' own gradient tensors: a reference held here makes the engine's next backward pass take them
-            # for gradients the caller still wants (it then leaves that arena alone and fills a new one, every step)
-            self._keep = (gtab, [g for g, p in zip(grads, plist) if g is not p.grad])
-            if len(plist) == len(group['params']) and all(g is p.grad for g, p in zip(grads, plist)):
+                buckets.setdefault(int(self.state[p]['step']), []).append(p)
+            for j, (prev, ps) in enumerate(sorted(buckets.items())):
+                slot = (gi, j)
+                tab = self._static_table(slot, ps)
+                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
+                gkey, gtab = self._grad_table(slot, grads)
+                step = prev + 1
+                for p in ps:
+                    self.state[p]['step'] = step
+                self._launch(tab, gtab, len(ps), group, step)
+                # keep alive until the next step (async launch): the pointer table and the contiguous COPIES made above --
+                # not the parameters' own gradient tensors: a reference held here makes the engine's next backward pass
+                # take them for gradients the caller still wants (it then leaves that arena alone and fills a new one,
+                # every step)
+                keep.append(gtab)
+                keep.extend(g for g, p in zip(grads, ps) if g is not p.grad)
+            for slot in [s for s in self._tables if s[0] == gi and s[1] >= len(buckets)]:
+                self._tables.pop(slot)
+                self._gtabs.pop(slot, None)
+            if len(buckets) == 1 and len(plist) == len(group['params']) and all(g is p.grad for g, p in zip(grads, plist)):
+                states = [self.state[p] for p in plist]
                 self._fast[gi] = dict(params=group['params'], n=len(plist), gkey=gkey,
                                       pkey=tuple(p.data_ptr() for p in plist), amsgrad=bool(group['amsgrad']),
-                                      step=step, states=[self.state[p] for p in plist], tab=tab, gtab=gtab)
+                                      step=step, states=states, tab=tab, gtab=gtab,
+                                      moments=[(s, s['exp_avg'], s['exp_avg_sq'], s.get('max_exp_avg_sq'))
+                                               for s in states])
+        self._keep = keep
         engine.PARAM_EPOCH[0] += 1                # parameters changed behind tensor._version's back
         return loss
