@@ -16,6 +16,13 @@
 //   5 lcc_write   out[i] = 1 where find(i) is the chosen root (nothing when no voxel is positive: the reference's
 //                 `if mask.max() > 0`)
 // Everything is integer and the result does not depend on the schedule.
+//
+// Batched form (aide_keep_largest_cc3d_batched, aide_case_confusion_batched): the label maps of K ragged cases concatenated
+// as [S_total][H][W] with a device table slice_start[K + 1].  Case k's logical volume is [H][W][S_k]; its voxel (h, w, s) is
+// node base_k + (h * W + w) * S_k + s with base_k = slice_start[k] * H * W, so a case owns a contiguous range of nodes whose
+// order is its own raster order: the same invariants, the same tie rule, and a union never leaves the range because a tile
+// never leaves its case.  Every launch has the grid (chunks of the plane, K): blockIdx.y is the case, the block walks the
+// case's slices, and the number of launches is the per-case form's five whatever K is.
 #include "common.h"
 
 namespace {
@@ -299,6 +306,266 @@ bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
     return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
 }
 
+
+// ---- batched over K ragged cases -------------------------------------------------------------------------------------
+struct Cases {
+    const long long* v;       // [S_total][H][W], contiguous
+    const long long* start;   // [K + 1] first slice of every case (device)
+    int S_total, H, W;
+    int tw;                   // 16-wide tiles along w
+};
+
+// slices [s0, s0 + ns) of case k; a table entry outside [0, S_total] or below its predecessor is clamped, so that no
+// address derived from it leaves the buffers
+__device__ __forceinline__ void case_range(const long long* start, int k, int S_total, int& s0, int& ns) {
+    long long a = start[k], b = start[k + 1];
+    a = a < 0 ? 0 : (a > S_total ? S_total : a);
+    b = b < a ? a : (b > S_total ? S_total : b);
+    s0 = (int)a;
+    ns = (int)(b - a);
+}
+
+// a 16 x 16 (h, w) tile of the plane per block, 4 slices at a time: thread t owns (h, w) = (t / 16, t % 16), local index
+// e = t * 4 + z -- (h, w, s) order, the raster order of the case
+__global__ __launch_bounds__(256) void lccb_local_kernel(Cases g, int* __restrict__ parent, int* __restrict__ area,
+                                                         unsigned long long* __restrict__ ctrl) {
+    __shared__ long long val[TILE];
+    __shared__ int lp[TILE];
+    __shared__ int cnt[TILE];
+    const int k = blockIdx.y, t = threadIdx.x, hl = t >> 4, wl = t & 15;
+    if (blockIdx.x == 0 && t == 0) { ctrl[2 * k] = 0ull; ctrl[2 * k + 1] = 0ull; }
+    int s0, ns;
+    case_range(g.start, k, g.S_total, s0, ns);
+    const int h = (int)(blockIdx.x / g.tw) * 16 + hl, w = (int)(blockIdx.x % g.tw) * 16 + wl;
+    const bool in_hw = h < g.H && w < g.W;
+    const long hw = (long)g.H * g.W;
+    const int base = (int)(s0 * hw), col = in_hw ? (h * g.W + w) * ns : 0;
+    for (int sc = 0; sc < ns; sc += TZ) {
+        __syncthreads();                          // the previous chunk's LDS is read to the end
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = t * TZ + z;
+            long long v = 0;
+            if (in_hw && sc + z < ns) v = g.v[(long)(s0 + sc + z) * hw + (long)h * g.W + w];
+            val[e] = v;
+            lp[e] = v != 0 ? e : -1;
+            cnt[e] = 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = t * TZ + z;
+            const long long v = val[e];
+            if (v == 0) continue;
+            if (z > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
+            if (wl > 0 && val[e - TZ] == v) lds_unite(lp, e - TZ, e);
+            if (hl > 0 && val[e - 16 * TZ] == v) lds_unite(lp, e - 16 * TZ, e);
+        }
+        __syncthreads();
+        int root[TZ];
+#pragma unroll
+        for (int z = 0; z < TZ; ++z) {
+            const int e = t * TZ + z;
+            root[z] = val[e] != 0 ? lds_find(lp, e) : -1;
+            if (root[z] >= 0) atomicAdd(&cnt[root[z]], 1);
+        }
+        __syncthreads();
+        if (in_hw) {
+#pragma unroll
+            for (int z = 0; z < TZ; ++z) {
+                if (sc + z >= ns) break;
+                const int e = t * TZ + z;
+                int gr = -1;
+                if (root[z] >= 0) {               // the lowest local index of the tile-blob is its lowest node
+                    const int r = root[z], rt = r / TZ, rh = rt >> 4, rw = rt & 15;
+                    gr = base + ((h - hl + rh) * g.W + (w - wl + rw)) * ns + sc + (r - rt * TZ);
+                }
+                parent[base + col + sc + z] = gr;
+                area[base + col + sc + z] = cnt[e];
+            }
+        }
+    }
+}
+
+// lower faces of every 16 x 16 x 4 chunk: w face (4 x 16 pairs), h face (4 x 16), s face (16 x 16)
+__global__ __launch_bounds__(256) void lccb_border_kernel(Cases g, int* __restrict__ parent) {
+    const int k = blockIdx.y;
+    int s0, ns;
+    case_range(g.start, k, g.S_total, s0, ns);
+    const int h0 = (int)(blockIdx.x / g.tw) * 16, w0 = (int)(blockIdx.x % g.tw) * 16;
+    const long hw = (long)g.H * g.W;
+    const int base = (int)(s0 * hw);
+    for (int sc = 0; sc < ns; sc += TZ) {
+        for (int q = threadIdx.x; q < 2 * TZ * 16 + 256; q += 256) {
+            int z, hl, wl, dz = 0, dh = 0, dw = 0;
+            if (q < TZ * 16) {
+                if (w0 == 0) continue;
+                z = q >> 4; hl = q & 15; wl = 0; dw = 1;
+            } else if (q < 2 * TZ * 16) {
+                if (h0 == 0) continue;
+                const int j = q - TZ * 16;
+                z = j >> 4; wl = j & 15; hl = 0; dh = 1;
+            } else {
+                if (sc == 0) continue;
+                const int j = q - 2 * TZ * 16;
+                hl = j >> 4; wl = j & 15; z = 0; dz = 1;
+            }
+            const int s = sc + z, h = h0 + hl, w = w0 + wl;
+            if (s >= ns || h >= g.H || w >= g.W) continue;
+            const long off = (long)(s0 + s) * hw + (long)h * g.W + w;
+            const long long v = g.v[off];
+            if (v == 0) continue;
+            if (g.v[off - dz * hw - dh * g.W - dw] != v) continue;
+            const int gi = base + (h * g.W + w) * ns + s;
+            unite(parent, gi - dz - (dh * g.W + dw) * ns, gi);
+        }
+    }
+}
+
+// the nodes of 256 plane positions of a case are one contiguous run: (see lcc_count_kernel)
+__global__ __launch_bounds__(256) void lccb_count_kernel(const long long* __restrict__ start, int S_total, int HW,
+                                                         int* __restrict__ parent, int* __restrict__ area) {
+    int s0, ns;
+    case_range(start, blockIdx.y, S_total, s0, ns);
+    const int p0 = (int)blockIdx.x * 256, np = min(256, HW - p0);
+    const int first = (int)((long)s0 * HW) + p0 * ns, count = np * ns;
+    for (int o = 0; o < count; o += 256) {        // whole waves: the trip count is the block's
+        const int j = o + (int)threadIdx.x, i = first + j;
+        int a = 0, r = -1;
+        if (j < count) {
+            a = area[i];
+            if (a > 0) {
+                r = find_plain(parent, i);
+                if (r != i) atomicMin(parent + i, r);
+                else a = 0;
+            }
+        }
+        unsigned long long pending = __ballot(a > 0);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int rl = __shfl(r, leader);
+            const bool mine = a > 0 && r == rl;
+            int s = mine ? a : 0;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+            if ((int)(threadIdx.x & 63) == leader) atomicAdd(area + rl, s);
+            if (mine) a = 0;
+            pending &= ~__ballot(mine);
+        }
+    }
+}
+
+// thread = one plane position of the case, all its slices (consecutive nodes); ctrl[2k] = max key, ctrl[2k + 1] = positive flag
+__global__ __launch_bounds__(256) void lccb_select_kernel(Cases g, const int* __restrict__ parent, const int* __restrict__ area,
+                                                          unsigned long long* __restrict__ ctrl) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    const int k = blockIdx.y;
+    int s0, ns;
+    case_range(g.start, k, g.S_total, s0, ns);
+    const long hw = (long)g.H * g.W;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long key = 0;
+    int pos = 0;
+    if (p < hw) {
+        const int first = (int)(s0 * hw + p * ns);
+        for (int s = 0; s < ns; ++s) {
+            const int i = first + s;
+            if (parent[i] != i) continue;
+            key = umax64(key, ((unsigned long long)(unsigned)area[i] << 32) | (unsigned)(0x7fffffff - i));
+            if (!pos) pos = g.v[(long)(s0 + s) * hw + p] > 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        key = umax64(key, __shfl_xor(key, o));
+        pos |= __shfl_xor(pos, o);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { sk[wid] = key; sp[wid] = pos; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        key = umax64(umax64(sk[0], sk[1]), umax64(sk[2], sk[3]));
+        pos = sp[0] | sp[1] | sp[2] | sp[3];
+        if (key) atomicMax(ctrl + 2 * k, key);
+        if (pos) atomicMax(ctrl + 2 * k + 1, 1ull);
+    }
+}
+
+__global__ __launch_bounds__(256) void lccb_write_kernel(const long long* __restrict__ start, int S_total, long hw,
+                                                         const int* __restrict__ parent,
+                                                         const unsigned long long* __restrict__ ctrl,
+                                                         unsigned char* __restrict__ out) {
+    const int k = blockIdx.y;
+    int s0, ns;
+    case_range(start, k, S_total, s0, ns);
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= hw) return;
+    const int best = ctrl[2 * k + 1] ? 0x7fffffff - (int)(unsigned)(ctrl[2 * k] & 0xffffffffull) : -1;
+    const int first = (int)(s0 * hw + p * ns);
+    for (int s = 0; s < ns; ++s) {
+        const int q = parent[first + s];
+        out[(long)(s0 + s) * hw + p] = (best >= 0 && q >= 0 && find_plain(parent, q) == best) ? 1 : 0;
+    }
+}
+
+// out[k][0..3] = N, sum p*t, sum p, sum t with t = (target byte == match); VEC: 16 bytes per load (hw % 16 == 0, aligned)
+template <bool VEC>
+__global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned char* __restrict__ p,
+                                                                const unsigned char* __restrict__ tg,
+                                                                const long long* __restrict__ start, int S_total, long hw,
+                                                                int match, long long* __restrict__ out) {
+    __shared__ long long sm[3][4];
+    const int k = blockIdx.y;
+    int s0, ns;
+    case_range(start, k, S_total, s0, ns);
+    const long n = ns * hw;
+    const unsigned char* pp = p + s0 * hw;
+    const unsigned char* tp = tg + s0 * hw;
+    long long spt = 0, sp = 0, st = 0;
+    if (VEC) {
+        for (long o = ((long)blockIdx.x * 256 + threadIdx.x) * 16; o < n; o += (long)gridDim.x * 256 * 16) {
+            const uint4 a = *reinterpret_cast<const uint4*>(pp + o);
+            const uint4 b = *reinterpret_cast<const uint4*>(tp + o);
+            const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+            unsigned c0 = 0, c1 = 0, c2 = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int sh = 0; sh < 32; sh += 8) {
+                    const unsigned x = (aw[j] >> sh) & 255u, m = ((bw[j] >> sh) & 255u) == (unsigned)match;
+                    c0 += m ? x : 0u; c1 += x; c2 += m;
+                }
+            spt += c0; sp += c1; st += c2;
+        }
+    } else {
+        for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long)gridDim.x * 256) {
+            const unsigned x = pp[o], m = tp[o] == (unsigned)match;
+            spt += m ? x : 0u; sp += x; st += m;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        spt += __shfl_xor(spt, o);
+        sp += __shfl_xor(sp, o);
+        st += __shfl_xor(st, o);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { sm[0][wid] = spt; sm[1][wid] = sp; sm[2][wid] = st; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const long long s = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(out + 4 * k + 1 + threadIdx.x), (unsigned long long)s);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 3) out[4 * k] = n;
+}
+
+// [S_total][H][W] with K cases: everything the grids and the node indices need fits an int
+bool batch_ok(int64_t S_total, int64_t H, int64_t W, int64_t K) {
+    if (S_total < 0 || H < 0 || W < 0 || K < 0 || K > 65535) return false;
+    return dims_ok(S_total, H, W);
+}
+
 }  // namespace
 
 extern "C" {
@@ -358,6 +625,61 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
         AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 9.0 * n, (confusion_kernel<long long, unsigned char>), grid, block, 0, stream, P, T, e1, e2, n, out);
     else
         AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 16.0 * n, (confusion_kernel<long long, long long>), grid, block, 0, stream, P, T, e1, e2, n, out);
+    return aide_launch_status();
+}
+
+size_t aide_lcc3d_batched_ws_bytes(int64_t nvox_total, int64_t K) {
+    if (nvox_total < 0 || nvox_total > INT32_MAX || K < 0 || K > 65535) return 0;
+    return (size_t)(2 * nvox_total) * sizeof(int) + 16 + (size_t)(2 * K) * sizeof(unsigned long long);
+}
+
+int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H,
+                                   int64_t W, unsigned char* out, void* ws, hipStream_t stream) {
+    if (!batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
+    const int n = (int)(S_total * H * W);
+    if (n == 0 || K == 0) return 0;
+    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    int* parent = static_cast<int*>(ws);
+    int* area = parent + n;
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    Cases g;
+    g.v = v; g.start = slice_start; g.S_total = (int)S_total; g.H = (int)H; g.W = (int)W;
+    g.tw = (int)((W + 15) / 16);
+    const long tiles = (long)g.tw * ((H + 15) / 16), chunks = (H * W + 255) / 256;
+    if (tiles > INT32_MAX) return AIDE_ERR_ARG;
+    const dim3 gt((unsigned)tiles, (unsigned)K), gc((unsigned)chunks, (unsigned)K), block(256);
+    const int hw = (int)(H * W);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 29.0 * n, lccb_local_kernel, gt, block, 0, stream, g, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_border_kernel, gt, block, 0, stream, g, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_count_kernel, gc, block, 0, stream, slice_start, (int)S_total, hw, parent, area);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_kernel, gc, block, 0, stream, g, (const int*)parent, (const int*)area,
+                      ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_write_kernel, gc, block, 0, stream, slice_start, (int)S_total, (long)hw,
+                      (const int*)parent, (const unsigned long long*)ctrl, out);
+    return aide_launch_status();
+}
+
+int aide_case_confusion_batched(const unsigned char* p, const unsigned char* t, const long long* slice_start, int64_t K,
+                                int64_t S_total, int64_t H, int64_t W, int match, long long* out, hipStream_t stream) {
+    if (!batch_ok(S_total, H, W, K) || match < 0 || match > 255) return AIDE_ERR_ARG;
+    if (K == 0) return 0;
+    if (!out || !slice_start) return AIDE_ERR_ARG;
+    const long hw = (long)(H * W);
+    if (S_total * hw > 0 && (!p || !t)) return AIDE_ERR_ARG;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)K * 4 * sizeof(long long), stream);
+    if (e != hipSuccess) return (int)e;
+    const bool vec = hw % 16 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(t)) & 15) == 0;
+    const long per = vec ? 4096 : 256;
+    const dim3 grid((unsigned)max(1L, min((hw + per - 1) / per * 4, 1024L)), (unsigned)K), block(256);
+    const double bytes = 2.0 * (double)S_total * (double)hw;
+    if (vec)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, confusion_batched_kernel<true>, grid, block, 0, stream, p, t, slice_start,
+                          (int)S_total, hw, match, out);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, confusion_batched_kernel<false>, grid, block, 0, stream, p, t, slice_start,
+                          (int)S_total, hw, match, out);
     return aide_launch_status();
 }
 

@@ -201,3 +201,102 @@ def case_scores(pred, target):
         dice = np.float64(2 * spt) / np.float64(sp + st)
         iou = np.float64(spt) / np.float64(sp + st - spt)
     return dict(Dice=dice, IoU=iou, TP=spt, TN=n - sp - st + spt, FP=sp - spt, FN=st - spt)
+
+
+# ---- all cases of an epoch at once (the epoch end of trainchaos_proposed_30cases1labeled.py:429-496) ----------------
+def _starts(slice_start, s_total):
+    """the host copy of a slice_start table as a list of ints, checked: K + 1 non-decreasing entries from 0 to S_total"""
+    st = [int(v) for v in (slice_start.tolist() if hasattr(slice_start, 'tolist') else slice_start)]
+    if len(st) < 1 or st[0] != 0 or st[-1] != s_total or any(b < a for a, b in zip(st, st[1:])):
+        raise RuntimeError('slice_start must rise from 0 to the slice count %d, got %r' % (s_total, st))
+    return st
+
+
+def keep_largest_batched(labels, slice_start):
+    """[S_total,H,W] integer label maps of K concatenated cases + slice_start[K+1] -> uint8 [S_total,H,W]: for every case
+    what `keep_largest_connected_components` gives for its [H,W,S_k] volume.  HIP tensors (slice_start an int64 HIP tensor:
+    the table is not read on the host): five launches for any K, no synchronisation.  Anything else: the CPU function per case."""
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        if labels.dim() != 3 or labels.dtype not in _INT_DTYPES:
+            raise RuntimeError('keep_largest_batched: [S,H,W] integer labels expected')
+        if labels.numel() > _MAX_VOX:
+            raise RuntimeError('keep_largest_batched: %d voxels, at most 2^31 - 1' % labels.numel())
+        if not (isinstance(slice_start, torch.Tensor) and slice_start.is_cuda and slice_start.dtype == torch.int64
+                and slice_start.dim() == 1 and slice_start.numel() >= 1 and slice_start.is_contiguous()):
+            raise RuntimeError('keep_largest_batched: slice_start must be a contiguous int64 HIP tensor [K + 1]')
+        v = labels.detach().to(torch.int64).contiguous()
+        k = slice_start.numel() - 1
+        out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
+        if v.numel() == 0 or k == 0:
+            return out.zero_()
+        ws = torch.empty(lib.aide_lcc3d_batched_ws_bytes(v.numel(), k), device=v.device, dtype=torch.uint8)
+        check(lib.aide_keep_largest_cc3d_batched(ptr(v), ptr(slice_start), k, *v.shape, ptr(out), ptr(ws), stream_ptr()),
+              'keep_largest_cc3d_batched')
+        return out
+    lab = np.asarray(labels)
+    st = _starts(slice_start, lab.shape[0])
+    out = np.zeros(lab.shape, np.uint8)
+    for a, b in zip(st, st[1:]):
+        if b > a:
+            out[a:b] = keep_largest_connected_components(lab[a:b].transpose(1, 2, 0)).transpose(2, 0, 1)
+    return out
+
+
+def case_dice_rule(sums, labelled=None, n_select=0):
+    """The host statement of `aide_label_refresh_select` (numpy): int64 sums [K,4] -> (dice float32 [K], rank int32 [K],
+    selected uint8 [K]).  dice = float32(float64(2 * sum p*t) / float64(sum p + sum t)); rank ascending with NaN greatest and
+    equal values by the lower index; selected = rank < n_select and not labelled."""
+    sums = np.asarray(sums, np.int64).reshape(-1, 4)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        dice = (np.float64(2) * sums[:, 1].astype(np.float64) / (sums[:, 2] + sums[:, 3]).astype(np.float64)).astype(np.float32)
+    key = np.where(np.isnan(dice), np.float32(np.inf), dice)
+    nan = np.isnan(dice).astype(np.int64)
+    order = np.lexsort((np.arange(len(dice)), key, nan))          # last key first: NaN flag, value, case index
+    rank = np.empty(len(dice), np.int32)
+    rank[order] = np.arange(len(dice), dtype=np.int32)
+    lab = np.zeros(len(dice), bool) if labelled is None else np.asarray(labelled).astype(bool)
+    return dice, rank, ((rank < int(n_select)) & ~lab).astype(np.uint8)
+
+
+def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None, n_select=0, keep_largest=True):
+    """Label maps [S_total,H,W] of K concatenated cases against one plane of the pseudo-label bank (uint8 [S_total,H,W]):
+    dict(filtered uint8 [S_total,H,W], sums int64 [K,4] = N / sum p*t / sum p / sum t with t = (bank byte == match),
+    dice float32 [K], rank int32 [K], selected uint8 [K]).  On HIP tensors seven launches, all results stay on the device and
+    nothing synchronises; slice_start / labelled are then device tables (int64 [K+1] / uint8 [K]).  On numpy / CPU inputs the
+    same integers through the CPU filter."""
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        filt = keep_largest_batched(labels, slice_start) if keep_largest else labels.to(torch.uint8).contiguous()
+        if not (isinstance(bank_plane, torch.Tensor) and bank_plane.is_cuda and bank_plane.dtype == torch.uint8
+                and bank_plane.is_contiguous() and tuple(bank_plane.shape) == tuple(filt.shape)):
+            raise RuntimeError('evaluate_label_maps: bank_plane must be a contiguous uint8 HIP tensor shaped like the labels')
+        if labelled is not None and not (isinstance(labelled, torch.Tensor) and labelled.is_cuda
+                                         and labelled.dtype == torch.uint8 and labelled.numel() == slice_start.numel() - 1):
+            raise RuntimeError('evaluate_label_maps: labelled must be a uint8 HIP tensor [K]')
+        k = slice_start.numel() - 1
+        dev = filt.device
+        sums = torch.empty(k, 4, device=dev, dtype=torch.int64)
+        dice = torch.empty(k, device=dev, dtype=torch.float32)
+        rank = torch.empty(k, device=dev, dtype=torch.int32)
+        sel = torch.empty(k, device=dev, dtype=torch.uint8)
+        check(lib.aide_case_confusion_batched(ptr(filt), ptr(bank_plane), ptr(slice_start), k, *filt.shape, int(match),
+                                              ptr(sums), stream_ptr()), 'case_confusion_batched')
+        check(lib.aide_label_refresh_select(ptr(sums), ptr(labelled) if labelled is not None else None, k, int(n_select),
+                                            ptr(dice), ptr(rank), ptr(sel), stream_ptr()), 'label_refresh_select')
+        return dict(filtered=filt, sums=sums, dice=dice, rank=rank, selected=sel)
+    lab = np.asarray(labels)
+    st = _starts(slice_start, lab.shape[0])
+    filt = keep_largest_batched(lab, st) if keep_largest else lab.astype(np.uint8)
+    t = np.asarray(bank_plane) == match
+    sums = np.zeros((len(st) - 1, 4), np.int64)
+    for k, (a, b) in enumerate(zip(st, st[1:])):
+        sums[k] = _confusion_host(filt[a:b], t[a:b])
+    dice, rank, sel = case_dice_rule(sums, labelled, n_select)
+    return dict(filtered=filt, sums=sums, dice=dice, rank=rank, selected=sel)
+
+
+def evaluate_cases(net, modal_inputs, slice_start, bank_plane, match=63, batch_size=16, labelled=None, n_select=0):
+    """All cases of an epoch in one pass: `modal_inputs` = (inphase[, outphase]), each [S_total,3,H,W] with the slices of the
+    K cases concatenated.  The forward batches may cross case boundaries (eval-mode BatchNorm: slices are independent);
+    filter, sums, Dice and ranking are `evaluate_label_maps`.  Nothing leaves the device."""
+    labels = predict_labels(net, *modal_inputs, batch_size=batch_size)
+    return evaluate_label_maps(labels, slice_start, bank_plane, match=match, labelled=labelled, n_select=n_select)

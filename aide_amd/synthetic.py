@@ -73,3 +73,31 @@ def chaos_batch(n, size=256, seed=1234, single_modal=False):
     if single_modal:
         return inphase, None, targets
     return inphase, outphase, targets
+
+
+CHAOS_LIVER = 63      # the liver's byte in the CHAOS mask PNGs (datasetchaos_proposed/dataset.py:9, palette[1])
+
+
+def chaos_cases(n_cases, size=256, seed=1234, slices=(3, 7), labelled=(0,), single_modal=False):
+    """A fixed synthetic case set for the label-refresh loop: K cases of ragged slice counts (uniform in `slices`, inclusive),
+    their slices concatenated.  -> dict(inphase / outphase f32 [S,3,H,W] (outphase None when single_modal), truth u8 [S,H,W]
+    (the mask PNG bytes: CHAOS_LIVER on the liver), initial u8 [S,H,W] (the truth for the labelled cases; for the others a
+    noisy pseudo-label: the truth shifted by a few pixels, with some slices emptied), slice_start [K + 1], labelled)."""
+    rng = np.random.RandomState(seed)
+    a, b, truth, initial, start = [], [], [], [], [0]
+    for k in range(n_cases):
+        ns = int(rng.randint(slices[0], slices[1] + 1))
+        dy, dx = (int(v) for v in rng.randint(-max(1, size // 16), max(1, size // 16) + 1, 2))
+        for _ in range(ns):
+            g1, g2, m = chaos_slice(rng, size)
+            a.append(_to_tensor_norm(g1))
+            if not single_modal:
+                b.append(_to_tensor_norm(g2))
+            m = (m * CHAOS_LIVER).astype(np.uint8)
+            truth.append(m)
+            noisy = np.roll(m, (dy, dx), (0, 1)) if rng.rand() >= 0.2 else np.zeros_like(m)
+            initial.append(m if k in labelled else noisy)
+        start.append(start[-1] + ns)
+    return dict(inphase=torch.stack(a), outphase=None if single_modal else torch.stack(b),
+                truth=torch.from_numpy(np.stack(truth)), initial=torch.from_numpy(np.stack(initial)),
+                slice_start=start, labelled=[k for k in labelled if k < n_cases])

@@ -60,6 +60,14 @@ _NET2_STREAM = {}
 # flipped by the angles reverseaug undoes.  Off: the scaled copies of the inputs (the measured default path).
 DEVICE_AUGMENT = [False]
 
+# AIDE's label self-correction (:429-496, :528-575).  Set: Train() draws a fixed synthetic case set once (aide_amd.synthetic.chaos_cases:
+# ragged cases, a few labelled, noisy initial pseudo-labels for the rest), samples every training batch from it with the two networks'
+# targets from the device-resident pseudo-label bank (aide_amd.labelbank), and at the epoch end evaluates all cases in one batched
+# pass and rewrites the worst quarter's pseudo-labels on the device.  Off: fixed targets and the one-case evaluation.
+REFRESH_LABELS = [False]
+REFRESH_CASES = [8]       # size of that case set
+LAST_BANK = [None]        # the bank of the last Train() that ran with the switch set (for inspection)
+
 
 def _device_views(aug, rng, n, size, seed, single, device):
     """one synthetic batch (the slices chaos_batch draws for `seed`) through LoaderAugment -> (inphase, outphase or None,
@@ -267,6 +275,17 @@ def Train(args=None, variant='chaos'):
         loader_aug = LoaderAugment(args.img_size, getattr(args, 'rotation', 60.0), getattr(args, 'data_mean', None),
                                    getattr(args, 'data_std', None))
         aug_rng = random.Random(args.torch_seed)
+    bank = None
+    if REFRESH_LABELS[0]:
+        from aide_amd.labelbank import PseudoLabelBank
+        from aide_amd.synthetic import chaos_cases
+        if world > 1:
+            raise ValueError('REFRESH_LABELS: per-replica BatchNorm statistics would let the ranks\' banks diverge; one process only')
+        if DEVICE_AUGMENT[0]:
+            raise ValueError('REFRESH_LABELS samples normalised slices of its case set; DEVICE_AUGMENT is not combined with it')
+        cs = chaos_cases(REFRESH_CASES[0], args.img_size, seed=args.torch_seed * 7919 + 29, single_modal=single)
+        bank = PseudoLabelBank(cs['initial'], cs['slice_start'], cs['labelled'], device=device)
+        case_in = (cs['inphase'].to(device),) if single else (cs['inphase'].to(device), cs['outphase'].to(device))
     best = 0.0                                                        # :244
     for epoch in range(args.num_epoch):
         ts = time.time()
@@ -277,7 +296,17 @@ def Train(args=None, variant='chaos'):
         l2 = torch.zeros((), device=device)
         for it in range(args.steps_per_epoch):
             seed = (args.torch_seed * 100003 + epoch * 1009 + it) * world + rank
-            if DEVICE_AUGMENT[0]:
+            t1 = t2 = None
+            if bank is not None:
+                # a batch of slices of the case set; targets1 / targets2 = plane 1 of the loader's one-hot of the CURRENT
+                # pseudo-labels of network 1 / 2 (:253-254 `mask1[:, 1]`, `mask2[:, 1]`)
+                idx = np.random.RandomState(seed).randint(0, cs['slice_start'][-1], args.batch_size)
+                didx = torch.from_numpy(idx).pin_memory().to(device, non_blocking=True)
+                xin, xout = case_in[0][didx], (None if single else case_in[1][didx])
+                t1, t2 = bank.targets(didx, 1)[:, 1].contiguous(), bank.targets(didx, 2)[:, 1].contiguous()
+                scale = [1 + 0.1 * float(torch.randn(1, generator=g)) for _ in range(4 if single else 8)]
+                augs = [xin * scale[k] for k in range(4)] if single else [(xin * scale[2 * k], xout * scale[2 * k + 1]) for k in range(4)]
+            elif DEVICE_AUGMENT[0]:
                 xin, xout, t, augs, augset = _device_views(loader_aug, aug_rng, args.batch_size, args.img_size, seed, single,
                                                            device)
             else:
@@ -289,6 +318,7 @@ def Train(args=None, variant='chaos'):
                     augs = [((xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device),
                              (xout * (1 + 0.1 * torch.randn(1, generator=g))).to(device)) for _ in range(4)]
                     xin, xout, t = xin.to(device), xout.to(device), t.to(device)
+            if bank is not None or not DEVICE_AUGMENT[0]:
                 # augmentation bookkeeping as the loader's dict (:81-95): 4 augmentations per sample, random flips and rotations
                 # within +-args.rotation; the logits are mapped back on the device (aide_reverse_aug)
                 augset = {'augno': [4] * args.batch_size}
@@ -296,7 +326,9 @@ def Train(args=None, variant='chaos'):
                     augset['hflip%d' % (k + 1)] = [int(torch.randint(0, 2, (1,), generator=g)) for _ in range(args.batch_size)]
                     augset['degree%d' % (k + 1)] = [float((torch.rand(1, generator=g) * 2 - 1) * args.rotation)
                                                     for _ in range(args.batch_size)]
-            r = coteach_step(net1, net2, opt1, opt2, loss_op, xin, xout, augs, t, t, rate, args.temperature, augset=augset,
+            if t1 is None:
+                t1 = t2 = t
+            r = coteach_step(net1, net2, opt1, opt2, loss_op, xin, xout, augs, t1, t2, rate, args.temperature, augset=augset,
                              pipeline=True, eval_aug=var['eval_aug'], sharpen=var['sharpen'])
             l1 += r['loss1']
             l2 += r['loss2']
@@ -305,8 +337,21 @@ def Train(args=None, variant='chaos'):
             sch1.step()
             sch2.step()
         # per-case evaluation of both networks and the best-checkpoint rule of :495-526 (average of the two case Dice values)
-        cd1 = evaluate_case(net1, args, device, single, epoch)
-        cd2 = evaluate_case(net2, args, device, single, epoch)
+        if bank is not None:
+            # :429-496 for all cases at once, then :528-575 on the device; the epoch's numbers as :495-496
+            net1.eval()
+            net2.eval()
+            wrote = bank.refresh(net1, net2, case_in, epoch, args.warmup_epoch)
+            net1.train()
+            net2.train()
+            dices = bank.case_dice()
+            cd1, cd2 = float(dices[0].sum() / float(bank.K)), float(dices[1].sum() / float(bank.K))
+            if wrote and rank == 0:
+                logging.info('Mask {} modify for net1'.format(bank.modify_list(1)))
+                logging.info('Mask {} modify for net2'.format(bank.modify_list(2)))
+        else:
+            cd1 = evaluate_case(net1, args, device, single, epoch)
+            cd2 = evaluate_case(net2, args, device, single, epoch)
         if rank == 0:
             logging.info('epoch %d loss1 %.4f loss2 %.4f traincase_dice %.3f %.3f time %.1fs', epoch + 1,
                          float(l1) / args.steps_per_epoch, float(l2) / args.steps_per_epoch, cd1, cd2, time.time() - ts)
@@ -317,6 +362,8 @@ def Train(args=None, variant='chaos'):
                     torch.save({'net': net.state_dict(), 'loss': float(l1 if k == 1 else l2) / args.steps_per_epoch,
                                 'epoch': epoch + 1},
                                os.path.join(args.checkpoint, var['ckpt'](args, names, k)))
+    if bank is not None:
+        LAST_BANK[0] = bank
     return net1, net2
 
 

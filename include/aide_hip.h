@@ -562,6 +562,42 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
                         int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
                         aide_stream_t stream);
 
+/* ---- the same for all cases of an epoch at once: K ragged cases concatenated as [S_total][H][W] (contiguous; what the
+ * label map yields when fed all slices) with a DEVICE table slice_start[K + 1] (int64, non-decreasing, slice_start[0] >= 0,
+ * slice_start[K] <= S_total; an entry outside that is clamped so that no access leaves the buffers).  Case k's logical
+ * volume is the reference's [H][W][S_k] (np.stack(..., axis=-1)), raster order (h, w, s).  K <= 65535,
+ * S_total * H * W < 2^31 (AIDE_ERR_ARG otherwise).  The number of launches does not depend on K. */
+/* workspace of aide_keep_largest_cc3d_batched (16-byte aligned); 0 when the arguments are out of range */
+size_t aide_lcc3d_batched_ws_bytes(int64_t nvox_total, int64_t K);
+/* out[S_total][H][W] (uint8) = per case what aide_keep_largest_cc3d gives for that case alone: components never cross a
+ * case boundary, one selection key per case, same tie rule within the case's raster order, all zeros for a case without
+ * a positive value.  Slices that belong to no case are not written.  Five launches. */
+int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H,
+                                   int64_t W, unsigned char* out, void* ws, aide_stream_t stream);
+/* out[K][4] (int64) = {N, sum p*t, sum p, sum t} per case with t = (target byte == match): p is the uint8 prediction, target
+ * a plane of the pseudo-label bank (match 63: the CHAOS liver plane mask[1] of the loader's palette one-hot).  One launch. */
+int aide_case_confusion_batched(const unsigned char* p, const unsigned char* target, const long long* slice_start, int64_t K,
+                                int64_t S_total, int64_t H, int64_t W, int match, long long* out, aide_stream_t stream);
+
+/* ---- pseudo-label bank: the label self-correction of trainchaos_proposed_30cases1labeled.py:528-575 without its PNG round
+ * trip.  The bank is [S_total][H][W] uint8 per network (the bytes of the `<mask>_netN.png` files the reference's loader
+ * reads, datasetchaos_proposed/dataset.py:37-56). */
+/* sums = aide_case_confusion_batched's out.  dice[k] = float32(2 * sums[k][1] / (sums[k][2] + sums[k][3])), the division in
+ * fp64 and rounded once (a numpy float64 stored into a float32 tensor, :488; 0 / 0 -> NaN).  rank[k] = position of case k in
+ * ascending order of dice, NaN greatest (torch's sort), equal values by the lower case index (this library's rule: the
+ * reference's sort is not stable).  selected[k] = rank[k] < n_select && !labelled[k] (labelled may be NULL).  K <= 4096.
+ * One launch of one workgroup. */
+int aide_label_refresh_select(const long long* sums, const unsigned char* labelled, int64_t K, int64_t n_select, float* dice,
+                              int* rank, unsigned char* selected, aide_stream_t stream);
+/* bank_plane[slices of k] = pred * scale (uint8; :548-551 with scale 63) for every case with selected[k] != 0, read on the
+ * device.  One launch. */
+int aide_label_bank_update(const unsigned char* pred, const unsigned char* selected, const long long* slice_start, int64_t K,
+                           int64_t S_total, int64_t H, int64_t W, int scale, unsigned char* bank_plane, aide_stream_t stream);
+/* out[N][npal][H][W] (int64) = one_hot_mask of bank_plane[slice_idx[n]] over the palette (npal = 1 .. 8 device ints): the
+ * loader's mask1 / mask2 (dataset.py:95-105).  A slice index outside [0, S_total) gives zeros.  N <= 65535.  One launch. */
+int aide_label_bank_targets(const unsigned char* bank_plane, int64_t S_total, int64_t H, int64_t W, const long long* slice_idx,
+                            int64_t N, const int* palette, int npal, long long* out, aide_stream_t stream);
+
 /* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
  * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
  * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
