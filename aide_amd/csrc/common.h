@@ -63,6 +63,11 @@ __device__ __forceinline__ float ld1(const bf16_store_t* p) { return __builtin_b
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_store_t* p, float v) { *p = (bf16_store_t)(cvt_pk_bf16(v, 0.f) & 0xffffu); }
 
+// two-class label of a pixel = argmax(softmax(z), dim=1): the softmax is monotonic, but its rounding merges logits closer than
+// ~2^-25 into equal probabilities, and argmax then returns the FIRST index: label 1 needs z1 > z0 *and* exp(z0 - z1) < 1 in
+// fp32 (a NaN logit gives 0).  Shared by aide_label_map and the per-image refresh epilogue, which must agree bit for bit.
+__device__ __forceinline__ int aide_label2(float z0, float z1) { return (z1 > z0 && expf(z0 - z1) < 1.0f) ? 1 : 0; }
+
 static inline int aide_launch_status() { return (int)hipGetLastError(); }
 
 // Dynamic-LDS opt-in (hipFuncAttributeMaxDynamicSharedMemorySize) of a launcher's kernels: once per DEVICE -- the attribute

@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long n = i / HW, p = i - n * HW;
         const float z0 = logits[n * l_bs + p], z1 = logits[n * l_bs + HW + p];
-        labels[i] = (z1 > z0 && expf(z0 - z1) < 1.0f) ? 1 : 0;
+        labels[i] = aide_label2(z0, z1);
     }
 }
 

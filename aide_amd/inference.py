@@ -300,3 +300,100 @@ def evaluate_cases(net, modal_inputs, slice_start, bank_plane, match=63, batch_s
     filter, sums, Dice and ranking are `evaluate_label_maps`.  Nothing leaves the device."""
     labels = predict_labels(net, *modal_inputs, batch_size=batch_size)
     return evaluate_label_maps(labels, slice_start, bank_plane, match=match, labelled=labelled, n_select=n_select)
+
+
+# ---- all IMAGES of an epoch (the epoch end of trainkidney_proposed_mask1.py:373-434 and
+# trainbreast_dataset3_proposed_272cases25labeled.py:373-438) -------------------------------------------------------------
+MAX_IMAGES = 1 << 20
+
+
+def image_dice_rule(sums, labelled=None, n_select=0):
+    """The host statement of `aide_image_refresh_select` (numpy): int64 sums [K,4] -> (dice float32 [K], rank int32 [K],
+    written uint8 [K]).  dice = 0.0 where sum p + sum t == 0 (Dice2d, :137-138: never NaN), else float32(float64(2 * sum p*t)
+    / float64(sum p + sum t)); rank ascending with equal values by the lower image index; written = rank < n_select and
+    sum p > 0 (:418 `if save_data.sum() > 0`) and not labelled."""
+    sums = np.asarray(sums, np.int64).reshape(-1, 4)
+    uni = sums[:, 2] + sums[:, 3]
+    dice = np.zeros(len(sums), np.float32)
+    nz = uni != 0
+    dice[nz] = ((2 * sums[nz, 1]).astype(np.float64) / uni[nz].astype(np.float64)).astype(np.float32)
+    order = np.lexsort((np.arange(len(dice)), dice))
+    rank = np.empty(len(dice), np.int32)
+    rank[order] = np.arange(len(dice), dtype=np.int32)
+    lab = np.zeros(len(dice), bool) if labelled is None else np.asarray(labelled).astype(bool)
+    return dice, rank, ((rank < int(n_select)) & (sums[:, 2] > 0) & ~lab).astype(np.uint8)
+
+
+def _image_eval_args(what, src, score_rows, gate, k0, pred, sums):
+    n, (h, w) = src.shape[0], src.shape[-2:]
+    k = pred.shape[0]
+    ok = (src.is_cuda and src.is_contiguous() and score_rows.is_cuda and score_rows.dtype == torch.uint8
+          and score_rows.is_contiguous() and tuple(score_rows.shape) == (n, h, w)
+          and pred.is_cuda and pred.dtype == torch.uint8 and pred.is_contiguous() and tuple(pred.shape) == (k, h, w)
+          and sums.is_cuda and sums.dtype == torch.int64 and sums.is_contiguous() and tuple(sums.shape) == (k, 4)
+          and (gate is None or (gate.is_cuda and gate.dtype == torch.uint8 and gate.is_contiguous() and gate.numel() == k))
+          and 0 <= k0 and k0 + n <= k <= MAX_IMAGES)
+    if not ok:
+        raise RuntimeError('%s: contiguous HIP tensors expected: score_rows uint8 [N,H,W], pred uint8 [K,H,W], sums int64 [K,4], '
+                           'gate uint8 [K] or None, k0 + N <= K <= 2^20' % what)
+    return n, h, w, k
+
+
+def image_eval_logits(logits, score_rows, gate, k0, pred, sums):
+    """The fused epilogue of a forward batch: logits [N,2,H,W] fp32 of the images k0 .. k0 + N - 1 -> pred[k0:k0 + N] =
+    `label_map(logits)` as uint8 and sums[k0:k0 + N] = (H*W, sum p*t, sum p, sum t) with t = (score_rows > 0) & gate.  No int64
+    label tensor exists at any point; nothing synchronises."""
+    if logits.dim() != 4 or logits.shape[1] != 2 or logits.dtype != torch.float32:
+        raise RuntimeError('image_eval_logits expects [N,2,H,W] fp32 logits')
+    logits = logits.detach()
+    if not logits.is_contiguous():
+        logits = logits.contiguous()
+    n, h, w, k = _image_eval_args('image_eval_logits', logits, score_rows, gate, k0, pred, sums)
+    check(lib.aide_image_eval_logits(ptr(logits), 2 * h * w, ptr(score_rows), ptr(gate) if gate is not None else None, n, h, w,
+                                     int(k0), k, ptr(pred), ptr(sums), stream_ptr()), 'image_eval_logits')
+
+
+def image_eval_labels(labels, score_rows, gate, k0, pred, sums):
+    """... from ready label maps [N,H,W] (uint8 or int64; p = label != 0), for `ImageLabelBank.refresh_from_labels`."""
+    if labels.dim() != 3 or labels.dtype not in (torch.uint8, torch.int64):
+        raise RuntimeError('image_eval_labels expects [N,H,W] uint8 or int64 label maps')
+    labels = labels.detach()
+    if not labels.is_contiguous():
+        labels = labels.contiguous()
+    n, h, w, k = _image_eval_args('image_eval_labels', labels, score_rows, gate, k0, pred, sums)
+    check(lib.aide_image_eval_labels(ptr(labels), int(labels.dtype == torch.uint8), ptr(score_rows),
+                                     ptr(gate) if gate is not None else None, n, h, w, int(k0), k, ptr(pred), ptr(sums),
+                                     stream_ptr()), 'image_eval_labels')
+
+
+def image_refresh_select(sums, labelled=None, n_select=0, out=None):
+    """int64 sums [K,4] on the device -> (dice float32 [K], rank int32 [K], written uint8 [K]) by `image_dice_rule`, for K up to
+    2^20: two launches, no host read.  out: the three tensors to fill."""
+    if not (sums.is_cuda and sums.dtype == torch.int64 and sums.dim() == 2 and sums.shape[1] == 4 and sums.is_contiguous()):
+        raise RuntimeError('image_refresh_select: sums must be a contiguous int64 HIP tensor [K,4]')
+    k = sums.shape[0]
+    if k > MAX_IMAGES:
+        raise RuntimeError('image_refresh_select: %d images, at most 2^20' % k)
+    if labelled is not None and not (labelled.is_cuda and labelled.dtype == torch.uint8 and labelled.is_contiguous()
+                                     and labelled.numel() == k):
+        raise RuntimeError('image_refresh_select: labelled must be a uint8 HIP tensor [K]')
+    if out is None:
+        out = (torch.empty(k, device=sums.device, dtype=torch.float32), torch.empty(k, device=sums.device, dtype=torch.int32),
+               torch.empty(k, device=sums.device, dtype=torch.uint8))
+    dice, rank, written = out
+    for t, dt in ((dice, torch.float32), (rank, torch.int32), (written, torch.uint8)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == k):
+            raise RuntimeError('image_refresh_select: out = (float32 [K], int32 [K], uint8 [K]) contiguous HIP tensors')
+    check(lib.aide_image_refresh_select(ptr(sums), ptr(labelled) if labelled is not None else None, k, int(n_select), ptr(dice),
+                                        ptr(rank), ptr(written), stream_ptr()), 'image_refresh_select')
+    return dice, rank, written
+
+
+def image_bank_update(pred, written, scale, plane):
+    """plane[k] = pred[k] * scale where written[k] (uint8 [K,H,W] planes, `written` read on the device)."""
+    ok = (pred.is_cuda and plane.is_cuda and written.is_cuda and pred.dtype == plane.dtype == written.dtype == torch.uint8
+          and pred.dim() == 3 and pred.shape == plane.shape and pred.is_contiguous() and plane.is_contiguous()
+          and written.is_contiguous() and written.numel() == pred.shape[0] <= MAX_IMAGES)
+    if not ok:
+        raise RuntimeError('image_bank_update: contiguous uint8 HIP tensors pred / plane [K,H,W] and written [K] expected')
+    check(lib.aide_image_bank_update(ptr(pred), ptr(written), *pred.shape, int(scale), ptr(plane), stream_ptr()), 'image_bank_update')

@@ -14,7 +14,10 @@ masks the same integers are computed with numpy (and the scipy filter): the form
 
 Ranking: ascending Dice, NaN greatest (as torch's sort), equal values by the lower case index.  The last is this
 project's rule: the reference's `Tensor.sort()` is not stable, so a tie at the selection boundary has no defined winner
-there."""
+there.
+
+`ImageLabelBank` is the per-IMAGE form of the kidney and breast scripts (no component filter, Dice2d with union == 0 -> 0.0,
+`--update_percent`, an empty prediction is never written; `aide_image_*` of csrc/labelbank_image.hip): see its docstring."""
 import os
 
 import numpy as np
@@ -171,3 +174,249 @@ class PseudoLabelBank(object):
                     Image.fromarray(bank[n, s], 'L').save(path)
                     written.append(path)
         return written
+
+
+# scoring targets of the two networks: (network 1, network 2), each 'original' or the index of a bank plane.
+#   breast: sample[2] = the original mask, sample[3] = network 1's pseudo-label (trainbreast_dataset3_proposed_272cases25labeled.py:380-381)
+#   kidney: sample[4] = network 2's, sample[3] = network 1's (trainkidney_proposed_mask1.py:380-381)
+IMAGE_FORMS = {
+    'breast': dict(score=('original', 0), scale=255, gated=False, skip_labelled=True),
+    'kidney': dict(score=(1, 0), scale=1, gated=True, skip_labelled=False),
+}
+
+
+class ImageLabelBank(object):
+    """The per-IMAGE label self-correction of the kidney and breast scripts (trainkidney_proposed_mask{1,2,3}.py:373-434,
+    trainbreast_dataset3_proposed_272cases25labeled.py:373-438).
+
+    original_masks_u8: [K,H,W] uint8, the original mask of every training image; both pseudo-label planes start as copies
+    of it (the loaders fall back to it while no `_net1` / `_net2` file exists).  labelled: indices of the images whose
+    labels are never rewritten (breast: `maskname not in labeled_cases`, :411; the kidney scripts have no such exception
+    and ignore it).  A HIP tensor (or device=...) keeps the bank on the device; numpy / CPU input keeps a numpy bank.
+
+    The rule, for network n, image k, p = argmax(softmax(logits)) in {0, 1}, t = the scoring target:
+      sums     sum p*t, sum p, sum t: exact integers
+      dice     0.0 if sum p + sum t == 0 (Dice2d never gives NaN), else float32(float64(2 sum p*t) / float64(sum p + sum t))
+      target   breast: network 1 against the ORIGINAL mask, network 2 against NETWORK 1's plane, t = byte > 0;
+               kidney: network 1 against NETWORK 2's plane, network 2 against NETWORK 1's, t = (byte > 0) & gate[k], where
+               gate[k] says that the original mask of image k is not constant: the kidney ToTensor multiplies every mask by
+               len(np.unique(original mask)) - 1 (datasetkidney_proposed/transform.py:96-104), so an image with a constant
+               original mask has all-zero targets whatever its pseudo-label planes hold
+      order    all four score vectors are taken BEFORE either network's planes are rewritten (network 2 reads network 1's)
+      ranking  ascending dice, equal values by the lower image index.  This is this project's rule: the reference's
+               `Tensor.sort()` is not stable.  Ties at 0.0 are COMMON here (every empty prediction against an empty
+               target scores 0.0), so which of them fall inside the worst n_select is decided by this rule, not by the reference
+      select   n_select = int(update_percent * K), the float product truncated as Python does
+      write    written[k] = rank[k] < n_select and sum p[k] > 0 (:418 `if save_data.sum() > 0`) [and not labelled[k]: breast]
+               while `refresh_gate(epoch, warmup_epoch)` is open: plane_n[k] = p * scale (255: breast PNGs, 1: kidney volumes)
+
+    The reference evaluates `train_dataset.__getitem__`, i.e. under the random training transform, and writes the labels in
+    that frame; in which frame `inputs` and the planes are is the caller's business."""
+
+    def __init__(self, original_masks_u8, labelled=None, form='breast', update_percent=0.25, device=None, image_ids=None):
+        if form not in IMAGE_FORMS:
+            raise ValueError("ImageLabelBank: form must be 'breast' or 'kidney'")
+        self.form = form
+        self._f = IMAGE_FORMS[form]
+        m = original_masks_u8
+        on_dev = isinstance(m, torch.Tensor) and m.is_cuda
+        if device is None and on_dev:
+            device = m.device
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type != 'cuda':
+            self.device = None
+        if m.dtype not in (torch.uint8, np.uint8) or len(m.shape) != 3:
+            raise RuntimeError('ImageLabelBank: [K,H,W] uint8 masks expected')
+        self.K, self.H, self.W = (int(v) for v in m.shape)
+        if self.K > (1 << 20):
+            raise RuntimeError('ImageLabelBank: %d images, at most 2^20' % self.K)
+        self.update_percent = float(update_percent)
+        self.n_select = int(self.update_percent * self.K)        # :403 / :406
+        if self.n_select < 0:
+            raise ValueError('ImageLabelBank: update_percent must not be negative')
+        lab = np.zeros(self.K, np.uint8)
+        if self._f['skip_labelled']:
+            for k in (labelled if labelled is not None else ()):
+                lab[int(k)] = 1
+        self.labelled_host = lab
+        self.image_ids = list(image_ids) if image_ids is not None else None
+        if self.image_ids is not None and len(self.image_ids) != self.K:
+            raise RuntimeError('ImageLabelBank: %d image ids for %d images' % (len(self.image_ids), self.K))
+        host = np.ascontiguousarray(m.cpu().numpy() if isinstance(m, torch.Tensor) else m)
+        flat = host.reshape(self.K, -1)
+        # computed once, from the ORIGINAL masks: len(np.unique(mask)) - 1 of the thresholded (0 / 255) mask is 1 or 0
+        gate = ((flat > 0).any(1) & (flat == 0).any(1)).astype(np.uint8) if flat.shape[1] else np.zeros(self.K, np.uint8)
+        self.gate_host = gate if self._f['gated'] else None
+        if self.device is not None:
+            dev = self.device
+            self.original = torch.as_tensor(m).to(dev).contiguous()
+            self.bank = torch.stack([self.original, self.original]).contiguous()
+            self._labelled = torch.from_numpy(lab).to(dev) if self._f['skip_labelled'] else None
+            self._gate = torch.from_numpy(gate).to(dev) if self._f['gated'] else None
+            self._pred = torch.zeros(2, self.K, self.H, self.W, device=dev, dtype=torch.uint8)
+            self._sums = torch.zeros(2, self.K, 4, device=dev, dtype=torch.int64)
+            self._dice = torch.zeros(2, self.K, device=dev, dtype=torch.float32)
+            self.rank = torch.zeros(2, self.K, device=dev, dtype=torch.int32)
+            self.written = torch.zeros(2, self.K, device=dev, dtype=torch.uint8)
+            self.modified = torch.zeros(2, self.K, device=dev, dtype=torch.uint8)
+        else:
+            self.original = host.copy()
+            self.bank = np.stack([host, host])
+            self._pred = np.zeros((2, self.K, self.H, self.W), np.uint8)
+            self._sums = np.zeros((2, self.K, 4), np.int64)
+            self._dice = np.zeros((2, self.K), np.float32)
+            self.rank = np.zeros((2, self.K), np.int32)
+            self.written = np.zeros((2, self.K), np.uint8)
+            self.modified = np.zeros((2, self.K), np.uint8)
+
+    def _score_plane(self, n):
+        s = self._f['score'][n]
+        return self.original if s == 'original' else self.bank[s]
+
+    # ---- epoch end ----
+    def _finish(self, epoch, warmup_epoch):
+        """Dice, ranking and write flags of both networks from the sums, THEN (gate open) the rewrite of both planes"""
+        write = refresh_gate(epoch, warmup_epoch)
+        if self.device is not None:
+            from .inference import image_refresh_select, image_bank_update
+            for n in (0, 1):
+                image_refresh_select(self._sums[n], self._labelled, self.n_select, out=(self._dice[n], self.rank[n], self.written[n]))
+            if write:
+                for n in (0, 1):
+                    image_bank_update(self._pred[n], self.written[n], self._f['scale'], self.bank[n])
+                self.modified.bitwise_or_(self.written)
+        else:
+            from .inference import image_dice_rule
+            for n in (0, 1):
+                self._dice[n], self.rank[n], self.written[n] = image_dice_rule(self._sums[n], self.labelled_host, self.n_select)
+            if write:
+                for n in (0, 1):
+                    w = self.written[n].astype(bool)
+                    self.bank[n][w] = self._pred[n][w] * np.uint8(self._f['scale'])       # :417-420 / :416-419
+                self.modified |= self.written
+        return write
+
+    def _host_sums(self, n, labels):
+        p = (np.asarray(labels) != 0).reshape(self.K, -1)
+        t = (self._score_plane(n) > 0).reshape(self.K, -1)
+        if self.gate_host is not None:
+            t = t & self.gate_host.astype(bool)[:, None]
+        self._pred[n] = p.reshape(self.K, self.H, self.W).astype(np.uint8)
+        self._sums[n, :, 0] = self.H * self.W
+        self._sums[n, :, 1] = (p & t).sum(1, dtype=np.int64)
+        self._sums[n, :, 2] = p.sum(1, dtype=np.int64)
+        self._sums[n, :, 3] = t.sum(1, dtype=np.int64)
+
+    def refresh_from_labels(self, labels1, labels2, epoch, warmup_epoch, batch_size=4096):
+        """labels1 / labels2: the two networks' label maps [K,H,W] (uint8 or int64, values 0 / 1) of all images.  Dice and
+        ranking are taken every epoch, from planes as they were BEFORE this call; the planes are rewritten only while the
+        gate is open.  -> whether it was.  On the device: no host synchronisation (`written` never leaves it)."""
+        if self.device is None:
+            for n, labels in enumerate((labels1, labels2)):
+                labels = labels.numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+                if tuple(labels.shape) != (self.K, self.H, self.W):
+                    raise RuntimeError('ImageLabelBank: label maps [%d,%d,%d] expected' % (self.K, self.H, self.W))
+                self._host_sums(n, labels)
+            return self._finish(epoch, warmup_epoch)
+        from .inference import image_eval_labels
+        for n, labels in enumerate((labels1, labels2)):
+            if not (isinstance(labels, torch.Tensor) and labels.is_cuda and tuple(labels.shape) == (self.K, self.H, self.W)):
+                raise RuntimeError('ImageLabelBank: the bank is on %s, the label maps [K,H,W] must be too' % self.device)
+            if labels.dtype not in (torch.uint8, torch.int64):
+                labels = labels.to(torch.int64)
+            plane = self._score_plane(n)
+            for i in range(0, self.K, batch_size):
+                image_eval_labels(labels[i:i + batch_size], plane[i:i + batch_size], self._gate, i, self._pred[n], self._sums[n])
+        return self._finish(epoch, warmup_epoch)
+
+    def refresh(self, net1, net2, inputs, epoch, warmup_epoch, batch_size=16):
+        """inputs: [K,3,H,W] (or a 1-tuple of it): both networks (eval mode) predict every image in batches; the logits of a
+        batch go straight through the fused epilogue (labels as uint8 + exact sums: no int64 label tensor of [K,H,W] exists),
+        then the rule.  Nothing synchronises with the host between prediction and update."""
+        if self.device is None:
+            raise RuntimeError('ImageLabelBank.refresh predicts on the device; a numpy bank takes refresh_from_labels')
+        from .inference import image_eval_logits
+        x = inputs[0] if isinstance(inputs, (tuple, list)) else inputs
+        if x.shape[0] != self.K or tuple(x.shape[-2:]) != (self.H, self.W):
+            raise RuntimeError('ImageLabelBank.refresh: inputs [%d,3,%d,%d] expected' % (self.K, self.H, self.W))
+        for n, net in enumerate((net1, net2)):
+            if net.training:
+                raise RuntimeError('ImageLabelBank.refresh needs net.eval(), as predict_labels does (:345-346)')
+            plane = self._score_plane(n)
+            with torch.no_grad():
+                for i in range(0, self.K, batch_size):
+                    logits = net(x[i:i + batch_size].to(self.device, non_blocking=True))
+                    image_eval_logits(logits, plane[i:i + batch_size], self._gate, i, self._pred[n], self._sums[n])
+        return self._finish(epoch, warmup_epoch)
+
+    def image_dice(self):
+        """float32 [2,K] on the host -- traindices1 / traindices2 of the last refresh (:392-393): ONE device-to-host copy.  The
+        epoch's numbers are then `d[n].sum() / float(K)` on the host (evaltrainavgdice1 / 2, :396-397)."""
+        return self._dice.cpu() if self.device is not None else torch.from_numpy(self._dice.copy())
+
+    def modify_count(self, net):
+        """the number of the reference's '{} masks modified for netN' line (:421, :438): len(sortidx[:n_select]), images that
+        were skipped (labelled, empty prediction) included.  No device read."""
+        if net not in (1, 2):
+            raise ValueError('net must be 1 or 2')
+        return min(self.n_select, self.K)
+
+    def written_images(self, net):
+        """indices of the images whose plane the last refresh rewrote (or would have, gate closed).  Copies K bytes."""
+        w = self.written[net - 1]
+        return np.flatnonzero(w.cpu().numpy() if self.device is not None else w).tolist()
+
+    # ---- next epoch ----
+    def targets(self, idx, net):
+        """int64 [N,H,W] targets of network `net`'s (1 or 2) pseudo-labels for the images `idx`: the loaders' mask1 / mask2
+        after ToTensor -- breast `byte > 0`, kidney `(byte > 0) & gate`.  An index outside [0, K) gives zeros."""
+        if net not in (1, 2):
+            raise ValueError('net must be 1 or 2')
+        plane = self.bank[net - 1]
+        if self.device is None:
+            idx = np.asarray(idx, np.int64).reshape(-1)
+            ok = (idx >= 0) & (idx < self.K)
+            t = plane[np.where(ok, idx, 0)] > 0
+            t &= ok[:, None, None]
+            if self.gate_host is not None:
+                t &= self.gate_host.astype(bool)[np.where(ok, idx, 0)][:, None, None]
+            return torch.from_numpy(t.astype(np.int64))
+        from ._lib import lib, check
+        from .ops import ptr, stream_ptr
+        idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+        if not idx.is_cuda:
+            idx = idx.pin_memory().to(self.device, non_blocking=True)
+        out = torch.empty(idx.numel(), self.H, self.W, device=self.device, dtype=torch.int64)
+        check(lib.aide_image_bank_targets(ptr(plane), self.K, self.H, self.W, ptr(idx), idx.numel(),
+                                          ptr(self._gate) if self._gate is not None else None, ptr(out), stream_ptr()),
+              'image_bank_targets')
+        return out
+
+    # ---- interchange ----
+    def export(self, root, writer=None):
+        """Writes the files the reference would have written so far, for every image that was rewritten for a network.
+        breast: `<root>/<caseid>/<caseid>_depth<d>_net{1,2}.png` through PIL (:412-420), image_ids[k] = (caseid, depth).
+        kidney: `writer(path, array)` with path `<root>/<folder>/<stem>_net{1,2}.nii.gz` and the int64 [1,H,W] array the
+        reference hands to SimpleITK (:412-419), image_ids[k] = (folder, stem); the caller supplies the writer.  -> the paths."""
+        ids = self.image_ids
+        if ids is None:
+            ids = [(str(k), 0) for k in range(self.K)] if self.form == 'breast' else [('0', str(k)) for k in range(self.K)]
+        if self.form == 'kidney' and writer is None:
+            raise RuntimeError('ImageLabelBank.export: the kidney form needs a writer(path, array)')
+        bank = self.bank.cpu().numpy() if self.device is not None else self.bank
+        mod = self.modified.cpu().numpy() if self.device is not None else self.modified
+        paths = []
+        for n in (0, 1):
+            for k in np.flatnonzero(mod[n]):
+                a, b = ids[k]
+                folder = os.path.join(root, str(a))
+                os.makedirs(folder, exist_ok=True)
+                if self.form == 'breast':
+                    from PIL import Image
+                    path = os.path.join(folder, '%s_depth%s_net%d.png' % (a, b, n + 1))
+                    Image.fromarray(bank[n, k]).save(path)
+                else:
+                    path = os.path.join(folder, '%s_net%d.nii.gz' % (b, n + 1))
+                    writer(path, bank[n, k][None].astype(np.int64))
+                paths.append(path)
+        return paths

@@ -43,12 +43,21 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+# The scripts' label self-correction (:373-438 / :373-434): per IMAGE, Dice2d, the worst int(--update_percent * K) images.  Set:
+# Train() draws a fixed synthetic image set once, samples every training batch from it with the two networks' targets from the
+# device-resident aide_amd.labelbank.ImageLabelBank, and at the epoch end scores all images and rewrites the selected ones on
+# the device.  Off (the default): fixed targets and the one-case evaluation.
+REFRESH_LABELS = [False]
+REFRESH_IMAGES = [24]     # size of that image set
+LAST_BANK = [None]        # the bank of the last Train() that ran with the switch set (for inspection)
+
 coteach_step = _core.coteach_step
 join_networks = _core.join_networks
 
 
 def Train(args=None):
-    return _core.Train(args or parse_args(), variant='breast')
+    refresh = dict(images=REFRESH_IMAGES[0], last=LAST_BANK) if REFRESH_LABELS[0] else None
+    return _core.Train(args or parse_args(), variant='breast', image_refresh=refresh)
 
 
 if __name__ == '__main__':

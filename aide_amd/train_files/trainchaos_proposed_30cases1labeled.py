@@ -228,7 +228,9 @@ def load_resumefile(path, nets):
     return True
 
 
-def Train(args=None, variant='chaos'):
+def Train(args=None, variant='chaos', image_refresh=None):
+    """image_refresh: None, or the kidney / breast mirrors' dict(images=N, last=[None]) when their REFRESH_LABELS switch is set: the
+    per-IMAGE label self-correction of those scripts (aide_amd.labelbank.ImageLabelBank) on a synthetic set of N images"""
     from aide_amd.optim import Adam
     from aide_amd.synthetic import chaos_batch
     from aide_amd.utils import CoTeachingProposedLoss
@@ -286,6 +288,22 @@ def Train(args=None, variant='chaos'):
         cs = chaos_cases(REFRESH_CASES[0], args.img_size, seed=args.torch_seed * 7919 + 29, single_modal=single)
         bank = PseudoLabelBank(cs['initial'], cs['slice_start'], cs['labelled'], device=device)
         case_in = (cs['inphase'].to(device),) if single else (cs['inphase'].to(device), cs['outphase'].to(device))
+    ibank = None
+    if image_refresh is not None:
+        from aide_amd.labelbank import ImageLabelBank
+        from aide_amd.synthetic import chaos_cases
+        if variant not in ('kidney', 'breast') or REFRESH_LABELS[0]:
+            raise ValueError('the per-image refresh belongs to the kidney and breast loops (and excludes the per-case one)')
+        if world > 1:
+            raise ValueError('REFRESH_LABELS: per-replica BatchNorm statistics would let the ranks\' banks diverge; one process only')
+        if DEVICE_AUGMENT[0]:
+            raise ValueError('REFRESH_LABELS samples normalised images of its image set; DEVICE_AUGMENT is not combined with it')
+        # one-slice cases: a fixed synthetic IMAGE set, a few labelled, noisy initial pseudo-labels for the rest
+        cs = chaos_cases(image_refresh['images'], args.img_size, seed=args.torch_seed * 7919 + 31, slices=(1, 1), labelled=(0, 5),
+                         single_modal=True)
+        ibank = ImageLabelBank(cs['initial'], labelled=cs['labelled'], form=variant, update_percent=args.update_percent,
+                               device=device)
+        case_in = (cs['inphase'].to(device),)
     best = 0.0                                                        # :244
     for epoch in range(args.num_epoch):
         ts = time.time()
@@ -297,13 +315,16 @@ def Train(args=None, variant='chaos'):
         for it in range(args.steps_per_epoch):
             seed = (args.torch_seed * 100003 + epoch * 1009 + it) * world + rank
             t1 = t2 = None
-            if bank is not None:
+            if bank is not None or ibank is not None:
                 # a batch of slices of the case set; targets1 / targets2 = plane 1 of the loader's one-hot of the CURRENT
                 # pseudo-labels of network 1 / 2 (:253-254 `mask1[:, 1]`, `mask2[:, 1]`)
                 idx = np.random.RandomState(seed).randint(0, cs['slice_start'][-1], args.batch_size)
                 didx = torch.from_numpy(idx).pin_memory().to(device, non_blocking=True)
                 xin, xout = case_in[0][didx], (None if single else case_in[1][didx])
-                t1, t2 = bank.targets(didx, 1)[:, 1].contiguous(), bank.targets(didx, 2)[:, 1].contiguous()
+                if ibank is not None:                      # the loaders' mask1 / mask2 after ToTensor (per image)
+                    t1, t2 = ibank.targets(didx, 1), ibank.targets(didx, 2)
+                else:
+                    t1, t2 = bank.targets(didx, 1)[:, 1].contiguous(), bank.targets(didx, 2)[:, 1].contiguous()
                 scale = [1 + 0.1 * float(torch.randn(1, generator=g)) for _ in range(4 if single else 8)]
                 augs = [xin * scale[k] for k in range(4)] if single else [(xin * scale[2 * k], xout * scale[2 * k + 1]) for k in range(4)]
             elif DEVICE_AUGMENT[0]:
@@ -318,7 +339,7 @@ def Train(args=None, variant='chaos'):
                     augs = [((xin * (1 + 0.1 * torch.randn(1, generator=g))).to(device),
                              (xout * (1 + 0.1 * torch.randn(1, generator=g))).to(device)) for _ in range(4)]
                     xin, xout, t = xin.to(device), xout.to(device), t.to(device)
-            if bank is not None or not DEVICE_AUGMENT[0]:
+            if bank is not None or ibank is not None or not DEVICE_AUGMENT[0]:
                 # augmentation bookkeeping as the loader's dict (:81-95): 4 augmentations per sample, random flips and rotations
                 # within +-args.rotation; the logits are mapped back on the device (aide_reverse_aug)
                 augset = {'augno': [4] * args.batch_size}
@@ -349,6 +370,19 @@ def Train(args=None, variant='chaos'):
             if wrote and rank == 0:
                 logging.info('Mask {} modify for net1'.format(bank.modify_list(1)))
                 logging.info('Mask {} modify for net2'.format(bank.modify_list(2)))
+        elif ibank is not None:
+            # trainkidney_proposed_mask1.py:373-434 / trainbreast_dataset3_proposed_272cases25labeled.py:373-438: every image
+            # scored, ranked and the worst rewritten on the device; evaltrainavgdice1 / 2 from the one copy of [2,K] floats
+            net1.eval()
+            net2.eval()
+            wrote = ibank.refresh(net1, net2, case_in, epoch, args.warmup_epoch)
+            net1.train()
+            net2.train()
+            dices = ibank.image_dice()
+            cd1, cd2 = float(dices[0].sum() / float(ibank.K)), float(dices[1].sum() / float(ibank.K))
+            if wrote and rank == 0:
+                logging.info('{} masks modified for net1'.format(ibank.modify_count(1)))      # (the reference's two spellings)
+                logging.info('{} masks modify for net2'.format(ibank.modify_count(2)))
         else:
             cd1 = evaluate_case(net1, args, device, single, epoch)
             cd2 = evaluate_case(net2, args, device, single, epoch)
@@ -364,6 +398,8 @@ def Train(args=None, variant='chaos'):
                                os.path.join(args.checkpoint, var['ckpt'](args, names, k)))
     if bank is not None:
         LAST_BANK[0] = bank
+    if ibank is not None:
+        image_refresh['last'][0] = ibank
     return net1, net2
 
 

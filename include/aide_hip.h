@@ -598,6 +598,38 @@ int aide_label_bank_update(const unsigned char* pred, const unsigned char* selec
 int aide_label_bank_targets(const unsigned char* bank_plane, int64_t S_total, int64_t H, int64_t W, const long long* slice_idx,
                             int64_t N, const int* palette, int npal, long long* out, aide_stream_t stream);
 
+/* ---- per-image pseudo-label bank: the label self-correction of trainkidney_proposed_mask{1,2,3}.py:373-434 and
+ * trainbreast_dataset3_proposed_272cases25labeled.py:373-438.  Every training IMAGE k of K <= 2^20 is scored with Dice2d
+ * (:131-141) and the worst int(update_percent * K) are rewritten.  Planes are [K][H][W] uint8, H * W < 2^31. */
+/* Fused epilogue of a forward batch: logits [N][2][H*W] fp32 (image stride l_bs floats) of the images k0 .. k0 + N - 1.
+ * pred[k0 + n] = the labels of aide_label_map on the same logits (bit-identical, equal logits and NaN included) as uint8;
+ * sums[k0 + n] = (H*W, sum p*t, sum p, sum t) int64 with t = (score_rows[n] byte > 0) & gate[k0 + n] (gate: K bytes, or NULL
+ * for 1).  score_rows: the N rows of the plane the network is scored against, [N][H*W].  Exact integers, whatever the order
+ * of the workgroups.  16-byte loads when H*W % 16 == 0 and all rows are 16-byte aligned, else a scalar path.
+ * One memset node and one launch. */
+int aide_image_eval_logits(const float* logits, int64_t l_bs, const unsigned char* score_rows, const unsigned char* gate,
+                           int64_t N, int64_t H, int64_t W, int64_t k0, int64_t K, unsigned char* pred, long long* sums,
+                           aide_stream_t stream);
+/* ... from ready label maps [N][H*W] (uint8 if is_u8, else int64) instead of logits: p = (label != 0). */
+int aide_image_eval_labels(const void* labels, int is_u8, const unsigned char* score_rows, const unsigned char* gate, int64_t N,
+                           int64_t H, int64_t W, int64_t k0, int64_t K, unsigned char* pred, long long* sums,
+                           aide_stream_t stream);
+/* dice[k] = 0 if sums[k][2] + sums[k][3] == 0, else float32(2 * sums[k][1] / (sums[k][2] + sums[k][3])) with the division in
+ * fp64 (Dice2d stored into a float32 tensor, :392).  rank[k] = position of image k in ascending order of dice, equal values
+ * by the lower image index (this library's rule: the reference's sort is not stable; NaN, which Dice2d cannot give, would
+ * rank greatest).  written[k] = rank[k] < n_select && sums[k][2] > 0 && !labelled[k] (labelled may be NULL): the `if
+ * save_data.sum() > 0` of :418.  Two launches for any K. */
+int aide_image_refresh_select(const long long* sums, const unsigned char* labelled, int64_t K, int64_t n_select, float* dice,
+                              int* rank, unsigned char* written, aide_stream_t stream);
+/* plane[k] = pred[k] * scale (uint8; 255 for the breast PNGs, 1 for the kidney volumes) for every image with written[k] != 0,
+ * read on the device.  One launch, a 1-D grid over (image, chunk). */
+int aide_image_bank_update(const unsigned char* pred, const unsigned char* written, int64_t K, int64_t H, int64_t W, int scale,
+                           unsigned char* plane, aide_stream_t stream);
+/* out[N][H][W] (int64) = (plane[image_idx[n]] > 0) & gate[image_idx[n]] (gate may be NULL): the loaders' mask1 / mask2 after
+ * ToTensor.  An index outside [0, K) gives zeros.  One launch. */
+int aide_image_bank_targets(const unsigned char* plane, int64_t K, int64_t H, int64_t W, const long long* image_idx, int64_t N,
+                            const unsigned char* gate, long long* out, aide_stream_t stream);
+
 /* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
  * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
  * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
