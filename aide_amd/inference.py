@@ -184,12 +184,57 @@ def _confusion_host(pred, target):
     return p.size, int(np.sum(p * t)), int(np.sum(p)), int(np.sum(t))
 
 
-def case_scores(pred, target):
+def _class_counts_device(pred, target, c):
+    """-> counts[C,3] int64 (numpy): one launch, one copy of C * 3 int64"""
+    _confusion_args(pred, target)
+    p, t = _as3d(pred), _as3d(target.to(pred.device))
+    out = torch.empty(c, 3, device=p.device, dtype=torch.int64)
+    check(lib.aide_mc_counts_labels(ptr(p), int(p.dtype == torch.uint8), *p.stride(), ptr(t), int(t.dtype == torch.uint8),
+                                    *t.stride(), *p.shape, c, ptr(out), stream_ptr()), 'mc_counts_labels')
+    return out.cpu().numpy()
+
+
+def _class_counts_host(pred, target, c):
+    p, t = np.asarray(pred).reshape(-1), np.asarray(target).reshape(-1)
+    if p.shape != t.shape:
+        raise RuntimeError('case_scores: shape mismatch %s vs %s' % (np.shape(pred), np.shape(target)))
+    out = np.zeros((c, 3), np.int64)
+    for k in range(c):
+        i, j = p == k, t == k
+        out[k] = (i & j).sum(), i.sum(), j.sum()
+    return out
+
+
+def _case_scores_classes(pred, target, c):
+    if not 2 <= c <= 8:
+        raise RuntimeError('case_scores: num_classes %d, 2 .. 8 are supported' % c)
+    dev = [x for x in (pred, target) if isinstance(x, torch.Tensor) and x.is_cuda]
+    if dev:
+        pred = torch.as_tensor(pred, device=dev[0].device)
+        target = torch.as_tensor(target, device=dev[0].device)
+        cnt = _class_counts_device(pred, target, c)
+    else:
+        pred, target = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (pred, target))
+        cnt = _class_counts_host(pred, target, c)
+    n = int(np.prod(np.shape(pred), dtype=np.int64))
+    tp, si, st = cnt[:, 0], cnt[:, 1], cnt[:, 2]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        dice = (2 * tp).astype(np.float64) / (si + st).astype(np.float64)
+        iou = tp.astype(np.float64) / (si + st - tp).astype(np.float64)
+    return dict(Dice=dice, IoU=iou, TP=tp.copy(), TN=n - si - st + tp, FP=si - tp, FN=st - tp)
+
+
+def case_scores(pred, target, num_classes=None):
     """Per-case scores of the evaluation script (evalchaos_comparison_1cases.py:116-141, 238-242) for a predicted label
     volume against its target: dict(Dice, IoU, TP, TN, FP, FN).  HIP tensors: one confusion launch and one copy of four
     int64 sums to the host; anything else: the same sums in int64 on the CPU.  TP = sum p*t, FP = sum p - TP,
     FN = sum t - TP, TN = N - sum p - sum t + TP (the reference's formulas, exact for any integers); Dice = 2 TP /
-    (sum p + sum t) and IoU = TP / (sum p + sum t - TP) as float64 true division like numpy's (0/0 -> nan, x/0 -> inf)."""
+    (sum p + sum t) and IoU = TP / (sum p + sum t - TP) as float64 true division like numpy's (0/0 -> nan, x/0 -> inf).
+    num_classes=C (2 .. 8): the same six scores per class for multi-class label volumes, as arrays of [C] (Dice, IoU float64,
+    the rest int64) with p_c = (pred == c), t_c = (target == c); a label outside [0, C) belongs to no class.  HIP tensors: one
+    launch of aide_mc_counts_labels and one copy of C * 3 int64."""
+    if num_classes is not None:
+        return _case_scores_classes(pred, target, int(num_classes))
     dev = [x for x in (pred, target) if isinstance(x, torch.Tensor) and x.is_cuda]
     if dev:
         pred = torch.as_tensor(pred, device=dev[0].device)

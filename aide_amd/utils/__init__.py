@@ -1,7 +1,8 @@
 # mirrors the reference's utils/__init__.py:1-10 for the hot-path symbols
 from .loss2d import (CrossEntropyLoss2d, DiceLoss, CEDiceLoss, CEMDiceLoss, MulticlassDiceLoss, Dice_Loss,  # noqa: F401
                      MulticlassMSELoss, CEMDiceLossImage)
-from .metrics2d import Dice_fn, Dice_fn_Nozero, TP_TN_FP_FN, IoU_fn  # noqa: F401
+from .metrics2d import (Dice_fn, IoU_fn, TP_TN_FP_FN, MulticlassDice_fn, MulticlassIoU_fn, MulticlassTP_TN_FP_FN,  # noqa: F401
+                        MulticlassAccuracy_fn, Dice_fn_Nozero, one_hot_result, multiclass_counts, MulticlassMeter)
 from .coteach_loss import (Coteachingloss_dropimage, Coteachingloss_weightimage, Coteachingloss_dropregionce,  # noqa: F401
                            Coteachingloss_dropimagedroppixel, KLbidirection, CoTeachingProposedLoss,
                            pseudo_label_ensemble)

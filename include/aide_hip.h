@@ -630,6 +630,37 @@ int aide_image_bank_update(const unsigned char* pred, const unsigned char* writt
 int aide_image_bank_targets(const unsigned char* plane, int64_t K, int64_t H, int64_t W, const long long* image_idx, int64_t N,
                             const unsigned char* gate, long long* out, aide_stream_t stream);
 
+/* ---- multi-class metrics (csrc/metrics_mc.hip): MulticlassDice_fn / MulticlassIoU_fn / MulticlassTP_TN_FP_FN /
+ * MulticlassAccuracy_fn of utils/metrics2d.py:86-196, which copy the logits to the host on every call (:87-91) and count with
+ * numpy.  Every one of them is a function of three integers per image and class: (sum i*t, sum i, sum t), i = one-hot of the
+ * prediction, t = one-hot of the target.  C = 2 .. 8; integer sums, the same bits from run to run. */
+/* counts[N][C][3] (int64) from logits [N][C][HW] fp32 (image stride l_bs floats, channels HW apart; N <= 65535, C * HW < 2^31).
+ * Prediction = torch.argmax(logits, dim=1) of the RAW logits (:89): equal maxima -> the lowest class; NaN is the greatest
+ * value and the first NaN wins.  (aide_label_map_mc is argmax(softmax(.)): its rounding merges close logits, so it has other
+ * ties.)  target (image stride t_bs elements), by t_kind: 0 one-hot [N][C][HW] float, 1 one-hot int64, 2 one-hot uint8 -- the
+ * loaders' 0/1-valued masks: any non-zero value is read as 1, soft targets are outside the contract; 3 class index [N][HW]
+ * int64 -- an index outside [0, C) belongs to no class, its pixel still counts in sum i.  counts need no zero-fill by the
+ * caller.  16-byte loads along HW when HW, l_bs, t_bs are multiples of 4 and both bases are aligned, else a scalar path.
+ * One memset node and one launch. */
+int aide_mc_counts_logits(const float* logits, int64_t l_bs, const void* target, int t_kind, int64_t t_bs, int C, int64_t N,
+                          int64_t HW, long long* counts, aide_stream_t stream);
+/* counts[C][3] (int64) for two label volumes of a case, i_c = (p == c), t_c = (t == c): operands and conventions of
+ * aide_case_confusion (int64 / uint8, logical dims with element strides, < 2^31 voxels); a label outside [0, C) belongs to no
+ * class.  Replaces per-class loops of Dice3d_fn / IoU3d_fn / TP_TN_FP_FN3d over `generatedtarget == c`
+ * (evalchaos_comparison_1cases.py:116-141).  One memset node and one launch. */
+int aide_mc_counts_labels(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                          int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, int C,
+                          long long* counts, aide_stream_t stream);
+/* acc += the N images of counts[N][C][3] (HW pixels each), added in index order by one workgroup: the float64 sums are the
+ * sequence the loops of metrics2d.py:124-133, 153-162 produce over the same images.  acc = 42 words of 8 bytes (8-byte
+ * aligned; the caller zeroes it once per epoch):
+ *   [0..7]   double  sum over images of Dice_c = 2 TP / (sum i + sum t), 1.0 when sum i + sum t == 0 (:130-131)
+ *   [8..15]  double  sum over images of IoU_c = TP / (sum i + sum t - TP), 1.0 likewise (:159-160)
+ *   [16..23] int64   sum TP_c      [24..31] int64 sum i_c      [32..39] int64 sum t_c
+ *   [40]     int64   images        [41]     int64 pixels (N * HW)
+ * classes >= C are not touched.  One fp64 division per term.  One launch. */
+int aide_mc_metrics_accumulate(const long long* counts, int64_t N, int C, int64_t HW, void* acc, aide_stream_t stream);
+
 /* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
  * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
  * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
