@@ -83,14 +83,9 @@ class Graph(object):
         self.ops.append(dict(kind='sa', src=src, dst=dst, mod=mod))
 
 
-# multiplies a launch executes per algorithmic (direct-convolution) multiply, by conv mode
-WINO_EXEC = 16.0 / 36.0
-BF16 = 16                      # conv mode id of the bf16-MFMA kernels (conv3x3_bf16.hip)
-EXEC_FRAC = {0: 1.0, 2: 16.0 / 36.0, 4: 36.0 / 144.0, BF16: 1.0}
-# profiler tags = the kernel that does the work of one conv operator call (its split reduce rides along)
-FWD_TAG = {0: 'conv3x3_mfma_kernel', 2: 'conv3x3_wino_kernel', 4: 'conv3x3_wino4_kernel', BF16: 'conv3x3_bf16_kernel'}
-WGRAD_TAG = {0: 'conv3x3_wgrad_kernel', 2: 'conv3x3_wgrad_wino_kernel', 4: 'conv3x3_wgrad4_kernel',
-             BF16: 'conv3x3_wgrad_bf16_kernel'}
+FAMILIES = ops.FAMILIES        # the 3x3-conv kernel families by conv mode: 0 direct, 2 / 4 Winograd F(2x2) / F(4x4), BF16
+BF16 = ops.BF16
+PACK_ORDER = (BF16, 4, 0, 2)   # issue order of the families' filter re-layout launches (part of the launch sequence)
 PRECISIONS = ('fp32', 'bf16')
 import os as _os
 
@@ -166,7 +161,7 @@ def conv_mode(cfg, n, cin, h, w, cout):
 
 
 # layer -> weight-gradient algorithm, for measurement only (tools/r6_wgrad_choice.py): {(cout, cin, h, w): 2 | 4}.  Empty in
-# the product: the static rule in Plan.__init__ decides.
+# the product: the static rule in select_conv decides.
 WGRAD_OVERRIDE = {}
 
 
@@ -175,6 +170,83 @@ def use_winograd(cfg, n, cin, h, w, cout):
     (tools/bench_conv.py all) has Winograd ahead on every layer shape it supports (1.2x-1.9x; the one
     exception, 64->128 @64x64 forward, loses 4 us), so it is used wherever it is supported."""
     return bool(cfg.use_winograd and lib.aide_conv3x3_wino_supported(cin, h, w, cout))
+
+
+def select_conv(cfg, precision, training, groups, n, cin, cout, h, w, need_dgrad, stem_only_so_far):
+    """The per-layer decisions of one 3x3 conv of a plan, from host-side queries of the library alone (no tensor, no stream, no
+    device): kernel family of the forward (wino_f), data-gradient (wino_d) and weight-gradient (wino_w) launches, their plans
+    (plan_f, plan_d: variant | splitk << 8) and split-K workspace bytes (sk_f, sk_d), the weight gradient's workgroup target
+    and workspace bytes (wg_target, wg_bytes), the BatchNorm statistics partials of the conv epilogue (stats_parts, 0 = none),
+    the eval-mode BatchNorm fold and the bf16 storage of z / dz.  h, w: the layer's plane; need_dgrad: the plan will run this
+    layer's data gradient; stem_only_so_far: every op before it in the graph is a stem conv without a data gradient."""
+    bf16 = precision == 'bf16'
+    d = dict(wg_target=0, stats_parts=0)
+    # Winograd F(2x2,3x3) where it is supported and measured faster (16 MFMA-multiplies
+    # per output instead of 36); the direct implicit GEMM otherwise
+    d['wino_f'] = conv_mode(cfg, n, cin, h, w, cout)
+    d['wino_d'] = conv_mode(cfg, n, cout, h, w, cin) if (need_dgrad and cfg.use_winograd_dgrad) else 0
+    # precision='bf16': bf16 operands / fp32 accumulation wherever the bf16 kernels cover the
+    # layer shape, the fp32 kernels elsewhere (narrow deep levels of small inputs)
+    if bf16 and FAMILIES[BF16].supported(cin, h, w, cout):
+        d['wino_f'] = BF16
+    if bf16 and need_dgrad and FAMILIES[BF16].supported(cout, h, w, cin):
+        d['wino_d'] = BF16
+    d['plan_f'] = FAMILIES[d['wino_f']].plan(n, cin, h, w, cout)
+    d['plan_d'] = FAMILIES[d['wino_d']].plan(n, cout, h, w, cin) if need_dgrad else 0
+    d['sk_f'] = lib.aide_conv3x3_ws_bytes(n, h, w, cout, d['plan_f'] >> 8)
+    d['sk_d'] = lib.aide_conv3x3_ws_bytes(n, h, w, cin, d['plan_d'] >> 8) if need_dgrad else 0
+    # weight gradient: transposed F(4x4,3x3) wherever supported (ahead on every layer of the sweep),
+    # else transposed F(2x2,3x3), else the direct kernel
+    if bf16 and FAMILIES[BF16].wgrad_supported(cout, cin, h, w):
+        d['wino_w'] = BF16
+    elif cfg.use_winograd and cfg.use_winograd4 and (cout % 64 == 0 or cfg.w4_half_tile) and \
+            WGRAD_OVERRIDE.get((cout, cin, h, w), 4) == 4 and FAMILIES[4].wgrad_supported(cout, cin, h, w):
+        # (a trailing half tile -- 32->32 @256x256 -- is 71 -> 56 us alone.  In round 2 the step lost 0.5 % with it:
+        # the 144 KB workgroups kept the main stream's kernels off the CUs; with the backward pass as it is now
+        # these layers are the last thing the weight-gradient stream does and the step gains: C2 621.9 / 620.9,
+        # 621.8 / 620.7, 621.2 / 619.6 same box, C3 level -- config.w4_half_tile)
+        d['wino_w'] = 4
+        # the LAST such launch of a backward pass whose dependent chain ends with it (every op before it in
+        # the graph is a stem conv without a data gradient -- the single-encoder U-Nets): nothing is left to
+        # share the chip with, so it takes all of it (the default leaves half to the dependent chain)
+        if stem_only_so_far:
+            d['wg_target'] = 256
+    elif cfg.use_winograd and FAMILIES[2].wgrad_supported(cout, cin, h, w):
+        d['wino_w'] = 2
+    else:
+        d['wino_w'] = 0
+    d['wg_bytes'] = FAMILIES[d['wino_w']].wgrad_ws_bytes(n, cout, cin, h, w, **_wgrad_extra(d))
+    # BatchNorm statistics from the conv epilogue (big planes, non-split F(4x4) forward, ungrouped training)
+    if training and (d['plan_f'] >> 8) <= 1 \
+            and (h * w) % 4 == 0 and lib.aide_bn_two_pass(n // max(groups, 1), cout, h, w):
+        # F(4x4) forward only.  The same epilogue in the direct and F(2x2) kernels was built and measured: C2
+        # 575 -> 572 images/s (their epilogues are short and the butterflies cost more than the saved pass) and
+        # the fp32 partial sums of the 3->64 stem at 320x320 (|mean| >> std) moved a gradient norm by 3e-3.
+        parts = lib.aide_conv3x3_wino4_stats_parts(n, h, w) if d['wino_f'] == 4 else 0
+        # (the same epilogue in the bf16 forward kernel -- sums of the stored bf16 z, one wave butterfly per
+        # channel tile -- was built in round 3 and measured: C5 444 -> 434 images/s, dropped)
+        d['stats_parts'] = max(parts, 0)
+    # eval mode (the per-case inference loop): BatchNorm of the running statistics + ReLU as the epilogue of the
+    # F(4x4) forward kernel -- the conv writes the activation, z is never materialised
+    d['fold'] = not training and cfg.fold_eval_bn and (
+        (d['wino_f'] == 4 and w != 16) or (d['wino_f'] == 0 and (d['plan_f'] >> 8) <= 1))
+    # bf16 mode keeps the conv output z (read only by BatchNorm) and its gradient dz (read only by the
+    # bf16 dgrad / wgrad kernels, which round it to bf16 anyway -- storing it narrow changes nothing
+    # numerically) in HBM as bf16: half the bytes of the conv-output write, of four BatchNorm reads and
+    # of the dz write + two reads
+    d['dz_bf16'] = (d['wino_w'] == BF16 and (not need_dgrad or d['wino_d'] == BF16) and cfg.store_bf16)
+    d['z_bf16'] = d['wino_f'] == BF16 and cfg.store_bf16
+    return d
+
+
+def _wgrad_extra(st):
+    """the family-specific arguments of a layer's weight-gradient launch and workspace query"""
+    return dict(target_wgs=256) if st.get('wg_target') else {}
+
+
+def _pack_slot(mode, direction):
+    """step key of a conv's filter pack of one direction ('f' | 'd'): 'wf' / 'wd' direct kernel, 'uf' / 'ud' the others"""
+    return ('u' if mode else 'w') + direction
 
 
 def _preferred(dev):
@@ -258,6 +330,7 @@ class Plan(object):
         self.grad = {}
         self.steps = []
         max_dz = max_wg = max_bnc = max_sk = 0
+        stem_only = True                 # every op so far is a stem conv without a data gradient (select_conv)
         for op in graph.ops:
             st = dict(op)
             if op['kind'] in ('conv', 'convT'):
@@ -272,95 +345,19 @@ class Plan(object):
                 if op['kind'] == 'conv':
                     cin = src.C
                     need_dg = not src.root.is_input and not forward_only
-                    # Winograd F(2x2,3x3) where it is supported and measured faster (16 MFMA-multiplies
-                    # per output instead of 36); the direct implicit GEMM otherwise
-                    st['wino_f'] = conv_mode(cfg, n, cin, hh, ww, cout)
-                    st['wino_d'] = conv_mode(cfg, n, cout, hh, ww, cin) if (need_dg and cfg.use_winograd_dgrad) else 0
-                    # precision='bf16': bf16 operands / fp32 accumulation wherever the bf16 kernels cover the
-                    # layer shape, the fp32 kernels elsewhere (narrow deep levels of small inputs)
-                    if bf16 and lib.aide_conv3x3_bf16_supported(cin, hh, ww, cout):
-                        st['wino_f'] = BF16
-                    if bf16 and need_dg and lib.aide_conv3x3_bf16_supported(cout, hh, ww, cin):
-                        st['wino_d'] = BF16
+                    sel = select_conv(cfg, precision, training, groups, n, cin, cout, hh, ww, need_dg, stem_only)
+                    max_sk = max(max_sk, sel.pop('sk_f'), sel.pop('sk_d'))
+                    st.update(sel)
                     st['wf'] = st['wd'] = st['uf'] = st['ud'] = None
-                    st['plan_f'] = st['plan_d'] = 0
-                    if st['wino_f'] == BF16:
-                        st['uf'] = pack_buf(conv, 'f', BF16, lambda: ops.bf16_pack_alloc(cout, cin, device))
-                        st['plan_f'] = lib.aide_conv3x3_bf16_splitk(n, cin, hh, ww, cout) << 8
-                    elif st['wino_f'] == 4:
-                        st['uf'] = pack_buf(conv, 'f', 4, lambda: torch.empty(cin, 36, cout, **f32))
-                        st['plan_f'] = lib.aide_conv3x3_wino4_splitk(n, cin, hh, ww, cout) << 8
-                    elif st['wino_f']:
-                        st['uf'] = pack_buf(conv, 'f', 2, lambda: torch.empty(ops.pad_to(cin, 8), 16, cout, **f32))
-                        st['plan_f'] = lib.aide_conv3x3_wino_splitk(n, cin, hh, ww, cout) << 8
-                    else:
-                        st['wf'] = pack_buf(conv, 'f', 0, lambda: torch.empty(ops.pad_to(cin, ops.conv_chunk(cin)), 9, cout, **f32))
-                        st['plan_f'] = lib.aide_conv3x3_plan(n, cin, hh, ww, cout)
-                    if need_dg and st['wino_d'] == BF16:
-                        st['ud'] = pack_buf(conv, 'd', BF16, lambda: ops.bf16_pack_alloc(cin, cout, device))
-                        st['plan_d'] = lib.aide_conv3x3_bf16_splitk(n, cout, hh, ww, cin) << 8
-                    elif need_dg and st['wino_d'] == 4:
-                        st['ud'] = pack_buf(conv, 'd', 4, lambda: torch.empty(cout, 36, cin, **f32))
-                        st['plan_d'] = lib.aide_conv3x3_wino4_splitk(n, cout, hh, ww, cin) << 8
-                    elif need_dg and st['wino_d']:
-                        st['ud'] = pack_buf(conv, 'd', 2, lambda: torch.empty(ops.pad_to(cout, 8), 16, cin, **f32))
-                        st['plan_d'] = lib.aide_conv3x3_wino_splitk(n, cout, hh, ww, cin) << 8
-                    elif need_dg:
-                        st['wd'] = pack_buf(conv, 'd', 0, lambda: torch.empty(ops.pad_to(cout, ops.conv_chunk(cout)), 9, cin, **f32))
-                        st['plan_d'] = lib.aide_conv3x3_plan(n, cout, hh, ww, cin)
-                    max_sk = max(max_sk, lib.aide_conv3x3_ws_bytes(n, hh, ww, cout, st['plan_f'] >> 8),
-                                 lib.aide_conv3x3_ws_bytes(n, hh, ww, cin, st['plan_d'] >> 8) if need_dg else 0)
-                    # weight gradient: transposed F(4x4,3x3) wherever supported (ahead on every layer of the sweep),
-                    # else transposed F(2x2,3x3), else the direct kernel
-                    if bf16 and lib.aide_conv3x3_wgrad_bf16_supported(cout, cin, hh, ww):
-                        st['wino_w'] = BF16
-                        st['wg_bytes'] = lib.aide_conv3x3_wgrad_bf16_ws_bytes(n, cout, cin, hh, ww, 0)
-                    elif cfg.use_winograd and cfg.use_winograd4 and (cout % 64 == 0 or cfg.w4_half_tile) and \
-                            WGRAD_OVERRIDE.get((cout, cin, hh, ww), 4) == 4 and \
-                            lib.aide_conv3x3_wgrad_wino4_supported(cout, cin, hh, ww):
-                        # (a trailing half tile -- 32->32 @256x256 -- is 71 -> 56 us alone.  In round 2 the step lost 0.5 % with it:
-                        # the 144 KB workgroups kept the main stream's kernels off the CUs; with the backward pass as it is now
-                        # these layers are the last thing the weight-gradient stream does and the step gains: C2 621.9 / 620.9,
-                        # 621.8 / 620.7, 621.2 / 619.6 same box, C3 level -- config.w4_half_tile)
-                        st['wino_w'] = 4
-                        # the LAST such launch of a backward pass whose dependent chain ends with it (every op before it in
-                        # the graph is a stem conv without a data gradient -- the single-encoder U-Nets): nothing is left to
-                        # share the chip with, so it takes all of it (the default leaves half to the dependent chain)
-                        if all(s0['kind'] == 'conv' and s0['src'].root.is_input for s0 in self.steps):
-                            st['wg_target'] = 256
-                        st['wg_bytes'] = lib.aide_conv3x3_wgrad_wino4_ws_bytes_t(n, cout, cin, hh, ww, st.get('wg_target', 0))
-                    elif cfg.use_winograd and lib.aide_conv3x3_wgrad_wino_supported(cout, cin, hh, ww):
-                        st['wino_w'] = 2
-                        st['wg_bytes'] = lib.aide_conv3x3_wgrad_wino_ws_bytes(n, cout, cin, hh, ww)
-                    else:
-                        st['wino_w'] = 0
-                        st['wg_bytes'] = lib.aide_conv3x3_wgrad_ws_bytes(n, cout, cin, hh, ww)
+                    for direction, ci, co in [('f', cin, cout)] + ([('d', cout, cin)] if need_dg else []):
+                        fam = FAMILIES[st['wino_' + direction]]
+                        st[_pack_slot(fam.mode, direction)] = pack_buf(conv, direction, fam.mode,
+                                                                       lambda: fam.pack_alloc(ci, co, device))
                     max_wg = max(max_wg, st['wg_bytes'])
-                    # BatchNorm statistics from the conv epilogue (big planes, non-split F(4x4) forward, ungrouped training)
-                    st['stats'] = None
-                    if training and (st['plan_f'] >> 8) <= 1 \
-                            and (hh * ww) % 4 == 0 and lib.aide_bn_two_pass(n // max(groups, 1), cout, hh, ww):
-                        # F(4x4) forward only.  The same epilogue in the direct and F(2x2) kernels was built and measured: C2
-                        # 575 -> 572 images/s (their epilogues are short and the butterflies cost more than the saved pass) and
-                        # the fp32 partial sums of the 3->64 stem at 320x320 (|mean| >> std) moved a gradient norm by 3e-3.
-                        parts = lib.aide_conv3x3_wino4_stats_parts(n, hh, ww) if st['wino_f'] == 4 else 0
-                        # (the same epilogue in the bf16 forward kernel -- sums of the stored bf16 z, one wave butterfly per
-                        # channel tile -- was built in round 3 and measured: C5 444 -> 434 images/s, dropped)
-                        if parts > 0:
-                            st['stats_parts'] = parts
-                            st['stats'] = torch.empty(cout * parts * 2, **f32)
-                    # eval mode (the per-case inference loop): BatchNorm of the running statistics + ReLU as the epilogue of the
-                    # F(4x4) forward kernel -- the conv writes the activation, z is never materialised
-                    st['fold'] = not training and cfg.fold_eval_bn and (
-                        (st['wino_f'] == 4 and ww != 16) or (st['wino_f'] == 0 and (st['plan_f'] >> 8) <= 1))
+                    st['stats'] = torch.empty(cout * st['stats_parts'] * 2, **f32) if st['stats_parts'] else None
                     st['pack_key'] = None
                     st['flops'] = 2.0 * n * hh * ww * cout * cin * 9      # algorithmic, per launch
-                    # bf16 mode keeps the conv output z (read only by BatchNorm) and its gradient dz (read only by the
-                    # bf16 dgrad / wgrad kernels, which round it to bf16 anyway -- storing it narrow changes nothing
-                    # numerically) in HBM as bf16: half the bytes of the conv-output write, of four BatchNorm reads and
-                    # of the dz write + two reads
-                    st['dz_bf16'] = (st['wino_w'] == BF16 and (not need_dg or st['wino_d'] == BF16) and cfg.store_bf16)
-                    if st['wino_f'] == BF16 and cfg.store_bf16:
+                    if st['z_bf16']:
                         st['z'] = torch.empty(n, cout, hh, ww, device=device, dtype=torch.bfloat16)
                 else:
                     cin = src.C
@@ -379,6 +376,7 @@ class Plan(object):
                 st['t4'] = torch.empty(n, 1, hh, ww, **f32)
                 st['gate'] = torch.empty(n, hh, ww, **f32)
                 st['stat'] = torch.empty(2, **f32)
+            stem_only = stem_only and op['kind'] == 'conv' and op['src'].root.is_input
             self.steps.append(st)
         self._plan_lazy_bn()
         self._plan_lazy_head()
@@ -693,36 +691,25 @@ class Plan(object):
         if cached is None:
             split = min(4, len(convs))
 
-            def tables(group, fwd=True, dgrad=True):
-                """pack tables of a group of convs; fwd / dgrad select which direction's packs they write"""
-                def pick(st, k, on):
-                    t = st[k] if on else None
-                    return None if (t is None or id(t) in fresh) else t
-                F = lambda st, k: pick(st, k, fwd)
-                D = lambda st, k: pick(st, k, dgrad)
-                direct = [(st['conv'].weight, F(st, 'wf'), D(st, 'wd')) for st in group
-                          if F(st, 'wf') is not None or D(st, 'wd') is not None]
+            def tables(group):
+                """{conv mode: pack table} of a group of convs, None if nothing of theirs needs a refresh"""
                 # a conv may use different modes forward and backward: each table gets only its own packs
-                def by_mode(mode):
-                    out = []
-                    for st in group:
-                        uf = F(st, 'uf') if st['wino_f'] == mode else None
-                        ud = D(st, 'ud') if st['wino_d'] == mode else None
-                        if uf is not None or ud is not None:
-                            out.append((st['conv'].weight, uf, ud))
-                    return out
-                wino, wino4, b16 = by_mode(2), by_mode(4), by_mode(BF16)
-                tabs = (ops.pack_table(direct, self.dev) if direct else None,
-                        ops.wino_pack_table(wino, self.dev) if wino else None,
-                        ops.wino4_pack_table(wino4, self.dev) if wino4 else None,
-                        ops.bf16_pack_table(b16, self.dev) if b16 else None)
-                return tabs if any(t is not None for t in tabs) else None
+                def pick(st, mode, direction):
+                    t = st[_pack_slot(mode, direction)] if st['wino_' + direction] == mode else None
+                    return None if (t is None or id(t) in fresh) else t
+                tabs = {}
+                for mode, fam in FAMILIES.items():
+                    entries = [(st['conv'].weight, pick(st, mode, 'f'), pick(st, mode, 'd')) for st in group]
+                    entries = [e for e in entries if e[1] is not None or e[2] is not None]
+                    if entries:
+                        tabs[mode] = ops._pack_table(fam, entries, self.dev)
+                return tabs or None
             rest = convs[split:]
             # (the dgrad-direction packs launched later, under the decoder forward, measured +-0 twice: one launch.  Round 6: the
             # whole re-layout of the level >= 2 filters started behind the first level instead of beside it -- the stems and the
             # 33 MB BatchNorm passes of level 0 run 3-8x slower next to it than alone -- 633.8 -> 629.1 images/s (C2), 398.6 ->
             # 397.1 (C4): the contention only moves to level 1.  Not kept.)
-            rest_tabs = tables(rest, True, True) if rest else None
+            rest_tabs = tables(rest) if rest else None
             cached = (tables(convs[:split]), rest_tabs, convs[split] if rest_tabs is not None else None)
             if len(self._pack_tabs) > 8:
                 self._pack_tabs.clear()
@@ -731,20 +718,9 @@ class Plan(object):
         self._gate_conv = gate
 
         def launch(tabs):
-            d, wn, w4, b16 = tabs
-            if b16 is not None:
-                ops.check(lib.aide_conv3x3_bf16_pack_multi(ops.ptr(b16[0]), b16[1], b16[2], ops.stream_ptr()),
-                          'conv3x3_bf16_pack_multi')
-            if w4 is not None:
-                ops.check(lib.aide_conv3x3_wino4_pack_multi(ops.ptr(w4[0]), w4[1], w4[2], ops.stream_ptr()),
-                          'conv3x3_wino4_pack_multi')
-            if d is not None:
-                ops.check(lib.aide_conv3x3_pack_weights_multi(ops.ptr(d[0]), d[1], d[2], ops.stream_ptr()),
-                          'conv3x3_pack_weights_multi')
-            if wn is not None:
-                ops.check(lib.aide_conv3x3_wino_pack_multi(ops.ptr(wn[0]), wn[1], wn[2], ops.stream_ptr()),
-                          'conv3x3_wino_pack_multi')
-        self._launch_pack = launch
+            for mode in PACK_ORDER:
+                if mode in tabs:
+                    ops.launch_pack_multi(FAMILIES[mode], tabs[mode])
         if fresh:
             # packs taken over from another plan: whatever stream(s) wrote them must be done before this forward reads them
             # (the same main stream in every flow of this package; a plan driven from another stream pays two waits)
@@ -850,7 +826,6 @@ class Plan(object):
         return out
 
     def _forward_impl(self, inputs, out, gate, tape):
-        import ctypes
         n = self.N
         if not self.training and (tape is not None or not self._coef_ok):
             # eval-mode coefficients of every BatchNorm, once per change of the parameters / running statistics (a replayed
@@ -958,87 +933,82 @@ class Plan(object):
 
     def _forward_op(self, st, inputs, out, bn_ws, sk_ws):
         kind = st['kind']
-        if True:
-            if kind == 'conv':
-                conv, bn = st['conv'], st['bn']
-                x = self.view(st['src'], inputs)
-                prof = self.profiler
-                if prof is not None:
-                    prof.begin(FWD_TAG[st['wino_f']], st['flops'], st['flops'] * EXEC_FRAC[st['wino_f']])
-                # training forward of a split-K layer: the conv leaves its slabs (accumulate = 2) and the BatchNorm that
-                # follows sums them itself -- no split-reduce launch, one pass over z less
-                slabs = self.training and (st['plan_f'] >> 8) > 1 and \
-                    (st['z'].shape[2] * st['z'].shape[3]) % 4 == 0          # (the slab loader reads 16 bytes)
-                acc = 2 if slabs else 0
-                if st.get('fold'):                 # eval: y = relu(acc * scale + folded bias) straight into the activation
-                    if st['wino_f'] == 4:
-                        ops.conv3x3_wino4(x, st['uf'], st['fbias'], self.view(st['dst']), accumulate=0,
-                                          splitk=st['plan_f'] >> 8, ws=sk_ws, epi_scale=st['scale'], epi_relu=True)
-                    else:                          # direct kernel (the 32-channel first level, the stems), non-split
-                        ops.conv3x3_igemm(x, st['wf'], st['fbias'], self.view(st['dst']), accumulate=0, plan=st['plan_f'],
-                                          ws=sk_ws, epi_scale=st['scale'], epi_relu=True)
-                    if prof is not None:
-                        prof.end()
-                    return
-                lazy = st.get('lazy_to')
-                in_tab = st.get('in_tab')               # this conv applies the BatchNorm + ReLU of its input's producer(s)
-                if st['wino_f'] == BF16:
-                    ops.conv3x3_bf16(x, st['uf'], conv.bias, st['z'], accumulate=acc, splitk=st['plan_f'] >> 8, ws=sk_ws)
-                elif st['wino_f'] == 4:
-                    # (st['stats']: this launch also writes the BatchNorm statistics partials of its output)
-                    ops.conv3x3_wino4(x, st['uf'], conv.bias, self.view(st['dst']) if lazy is not None else st['z'],
-                                      accumulate=acc, splitk=st['plan_f'] >> 8, ws=sk_ws, stats=st['stats'],
-                                      in_tab=in_tab, in_group_images=(self.N // self.groups) if in_tab is not None else 0)
-                elif st['wino_f']:
-                    ops.conv3x3_wino(x, st['uf'], conv.bias, st['z'], accumulate=acc, splitk=st['plan_f'] >> 8, ws=sk_ws)
-                else:
-                    ops.conv3x3_igemm(x, st['wf'], conv.bias, st['z'], accumulate=acc, plan=st['plan_f'], ws=sk_ws)
+        if kind == 'conv':
+            conv, bn = st['conv'], st['bn']
+            x = self.view(st['src'], inputs)
+            fam = FAMILIES[st['wino_f']]
+            pack = st[_pack_slot(fam.mode, 'f')]
+            prof = self.profiler
+            if prof is not None:
+                prof.begin(fam.fwd_tag, st['flops'], st['flops'] * fam.exec_frac)
+            # training forward of a split-K layer: the conv leaves its slabs (accumulate = 2) and the BatchNorm that
+            # follows sums them itself -- no split-reduce launch, one pass over z less
+            slabs = self.training and (st['plan_f'] >> 8) > 1 and \
+                (st['z'].shape[2] * st['z'].shape[3]) % 4 == 0          # (the slab loader reads 16 bytes)
+            acc = 2 if slabs else 0
+            if st.get('fold'):                 # eval: y = relu(acc * scale + folded bias) straight into the activation
+                # (F(4x4), or the direct kernel -- the 32-channel first level, the stems -- non-split: select_conv)
+                fam.conv(x, pack, st['fbias'], self.view(st['dst']), accumulate=0, plan=st['plan_f'], ws=sk_ws,
+                         epi_scale=st['scale'], epi_relu=True)
                 if prof is not None:
                     prof.end()
-                if st.get('head_lazy'):            # statistics -> (scale, shift); the head applies them while it reads z
-                    zn, zc, zh, zw = st['z'].shape
-                    ops.bn_finalize_groups(zn, 1, zc, zh, zw, bn, st['stats'], st['stats_parts'], st['stats_parts'], conv.bias,
-                                           st['mean'], st['rstd'], st['scale'], st['shift'], st['head_tab'], 0)
-                elif lazy is not None:               # statistics -> the reader's (scale, shift) table; no pass over the tensor
-                    zz = self.view(st['dst'])
-                    ops.bn_finalize_groups(self.N // self.groups, self.groups, zz.shape[1], zz.shape[2], zz.shape[3], bn,
-                                           st['stats'], st['stats_parts'] // self.groups, st['stats_parts'], conv.bias,
-                                           st['mean'], st['rstd'], st['scale'], st['shift'], lazy['in_tab'], st['tab_c0'])
-                else:
-                    self._bn_apply(st, bn, conv.bias if slabs else None, (st['plan_f'] >> 8) if slabs else 0, bn_ws, sk_ws)
-            elif kind == 'convT':
-                conv, bn = st['conv'], st['bn']
-                ops.convT2x2_fwd(self.view(st['src'], inputs), conv.weight, conv.bias, st['z'])
-                self._bn_apply(st, bn, None, 0, bn_ws, sk_ws)
-            elif kind == 'pool':
-                if not (st.get('fwd_fused') and self.training):
-                    ops.maxpool2x2_fwd(self.view(st['src'], inputs), self.view(st['dst']))
-            elif kind == 'up':
-                ops.upsample2x_fwd(self.view(st['src'], inputs), self.view(st['dst']))
-            elif kind == 'head':
-                conv = st['conv']
-                lp = st.get('lazy_prod')
-                if lp is not None:
-                    ops.head1x1_fwd_bn(lp['z'], lp['scale'], lp['shift'], conv.weight.view(conv.out_channels, -1), conv.bias, out)
-                else:
-                    ops.head1x1_fwd(self.view(st['src'], inputs), conv.weight.view(conv.out_channels, -1),
-                                    conv.bias, out)
-            elif kind == 'sa':
-                m = st['mod']
-                y = self.view(st['src'], inputs)
-                dil = m.conv2.dilation[0]
-                ops.pwconv_fwd(y, m.conv1.weight, m.conv1.bias, st['t1'])
-                ops.dconv_small(st['t1'], m.conv2.weight, m.conv2.bias, st['t2'], dil)
-                ops.dconv_small(st['t2'], m.conv3.weight, m.conv3.bias, st['t3'], dil)
-                ops.pwconv_fwd(st['t3'], m.conv4.weight, m.conv4.bias, st['t4'])
-                if self.training and self.groups > 1:
-                    mg = self.N // self.groups
-                    for gi in range(self.groups):
-                        ops.sa_gate_fwd(st['t4'][gi * mg:(gi + 1) * mg], m.bn, True, st['stat'],
-                                        st['gate'][gi * mg:(gi + 1) * mg])
-                else:
-                    ops.sa_gate_fwd(st['t4'], m.bn, self.training, st['stat'], st['gate'])
-                ops.sa_mul(st['gate'], y, self.view(st['dst']))
+                return
+            lazy = st.get('lazy_to')
+            y, only4 = st['z'], {}
+            if fam.mode == 4:
+                # F(4x4) only.  st['stats']: this launch also writes the BatchNorm statistics partials of its output; in_tab:
+                # it applies the BatchNorm + ReLU of its input's producer(s); lazy: its raw output goes to its reader's input
+                in_tab = st.get('in_tab')
+                only4 = dict(stats=st['stats'], in_tab=in_tab, in_group_images=(self.N // self.groups) if in_tab is not None else 0)
+                if lazy is not None:
+                    y = self.view(st['dst'])
+            fam.conv(x, pack, conv.bias, y, accumulate=acc, plan=st['plan_f'], ws=sk_ws, **only4)
+            if prof is not None:
+                prof.end()
+            if st.get('head_lazy'):            # statistics -> (scale, shift); the head applies them while it reads z
+                zn, zc, zh, zw = st['z'].shape
+                ops.bn_finalize_groups(zn, 1, zc, zh, zw, bn, st['stats'], st['stats_parts'], st['stats_parts'], conv.bias,
+                                       st['mean'], st['rstd'], st['scale'], st['shift'], st['head_tab'], 0)
+            elif lazy is not None:               # statistics -> the reader's (scale, shift) table; no pass over the tensor
+                zz = self.view(st['dst'])
+                ops.bn_finalize_groups(self.N // self.groups, self.groups, zz.shape[1], zz.shape[2], zz.shape[3], bn,
+                                       st['stats'], st['stats_parts'] // self.groups, st['stats_parts'], conv.bias,
+                                       st['mean'], st['rstd'], st['scale'], st['shift'], lazy['in_tab'], st['tab_c0'])
+            else:
+                self._bn_apply(st, bn, conv.bias if slabs else None, (st['plan_f'] >> 8) if slabs else 0, bn_ws, sk_ws)
+        elif kind == 'convT':
+            conv, bn = st['conv'], st['bn']
+            ops.convT2x2_fwd(self.view(st['src'], inputs), conv.weight, conv.bias, st['z'])
+            self._bn_apply(st, bn, None, 0, bn_ws, sk_ws)
+        elif kind == 'pool':
+            if not (st.get('fwd_fused') and self.training):
+                ops.maxpool2x2_fwd(self.view(st['src'], inputs), self.view(st['dst']))
+        elif kind == 'up':
+            ops.upsample2x_fwd(self.view(st['src'], inputs), self.view(st['dst']))
+        elif kind == 'head':
+            conv = st['conv']
+            lp = st.get('lazy_prod')
+            if lp is not None:
+                ops.head1x1_fwd_bn(lp['z'], lp['scale'], lp['shift'], conv.weight.view(conv.out_channels, -1), conv.bias, out)
+            else:
+                ops.head1x1_fwd(self.view(st['src'], inputs), conv.weight.view(conv.out_channels, -1),
+                                conv.bias, out)
+        elif kind == 'sa':
+            m = st['mod']
+            y = self.view(st['src'], inputs)
+            dil = m.conv2.dilation[0]
+            ops.pwconv_fwd(y, m.conv1.weight, m.conv1.bias, st['t1'])
+            ops.dconv_small(st['t1'], m.conv2.weight, m.conv2.bias, st['t2'], dil)
+            ops.dconv_small(st['t2'], m.conv3.weight, m.conv3.bias, st['t3'], dil)
+            ops.pwconv_fwd(st['t3'], m.conv4.weight, m.conv4.bias, st['t4'])
+            if self.training and self.groups > 1:
+                mg = self.N // self.groups
+                for gi in range(self.groups):
+                    ops.sa_gate_fwd(st['t4'][gi * mg:(gi + 1) * mg], m.bn, True, st['stat'],
+                                    st['gate'][gi * mg:(gi + 1) * mg])
+            else:
+                ops.sa_gate_fwd(st['t4'], m.bn, self.training, st['stat'], st['gate'])
+            ops.sa_mul(st['gate'], y, self.view(st['dst']))
 
     def _bn_apply(self, st, bn, slab_bias=None, splitk=0, bn_ws=None, sk_ws=None):
         """BatchNorm(+ReLU) of one conv output.  splitk > 0: z is still in the split-K slabs of self.sk_ws
@@ -1059,7 +1029,6 @@ class Plan(object):
                                         parts=st['stats'], nparts=st['stats_parts'] // ngroups,
                                         parts_stride=st['stats_parts'], conv_bias=st['conv'].bias)
             elif splitk > 0:
-                import ctypes
                 ops.bn_train_fwd_groups(z, a, ngroups, bn, st['mean'], st['rstd'], st['scale'], st['shift'], bn_ws,
                                         slabs=ctypes.c_void_p(sk_ws.data_ptr()), splitk=splitk, split_stride=z.numel(),
                                         slab_bias=slab_bias)
@@ -1078,7 +1047,6 @@ class Plan(object):
                                            st['mean'], st['rstd'], st['scale'], st['shift'], True,
                                            first=gi * gparts, stride=st['stats_parts'])
                 elif splitk > 0:
-                    import ctypes
                     sl = ctypes.c_void_p(sk_ws.data_ptr() + 4 * gi * m * per_img)
                     ops.bn_train_fwd_slabs(sl, splitk, stride, slab_bias, zg, ag, bn.weight, bn.bias, bn.eps, bn.momentum,
                                            bn.running_mean, bn.running_var, bn.num_batches_tracked, st['mean'],
@@ -1144,7 +1112,6 @@ class Plan(object):
         # raw stream handles: every fork / join below is a C-ABI call (ops.order) and every side-stream launch takes the
         # stream explicitly (ops.use_stream) -- nothing here depends on torch's stream context, so the whole sequence can be
         # recorded and re-issued by a launch tape
-        import ctypes
         mp = ctypes.c_void_p(main.cuda_stream)
         sp = ctypes.c_void_p(side.cuda_stream) if side is not None else None
         if side is not None:
@@ -1198,173 +1165,145 @@ class Plan(object):
             if after_op is not None:
                 after_op(st)
 
+    def _wgrad_handover(self, st, wgrad, tail, done, main, side):
+        """run a layer's weight gradient `wgrad()`: on the weight-gradient stream once its dz exists (`done`: the event of the
+        BatchNorm backward's last dispatch, else one recorded here), or in place (no such stream, or the tail op of the pass)"""
+        if side is None or tail:
+            return wgrad()
+        if done is not None:
+            ops.wait(side, done)
+        else:
+            ops.order(st['ev'], main, side)
+        with ops.use_stream(side):
+            wgrad()
+
     def _backward_op(self, st, inputs, dlogits, gslot, main, side, bn_ws, sk_ws, folded):
         """one op of the backward sequence on stream `main` (its lane's stream); folded: [split count] cell of the lane"""
-        if True:
-            kind = st['kind']
-            sg = st.get('src_grad')
-            if sg is not None:
-                for gap in sg['gaps']:
-                    ops.fill_zero(self.gview(gap))
-            if kind == 'head':
-                conv = st['conv']
-                k = conv.out_channels
-                assert sg is None or not sg['accumulate']
-                fused = bool(st.get('dgrad_fused'))     # the data gradient is formed by the BatchNorm backward of the layer below
-                dsrc = self.gview(st['src']) if (sg is not None and not fused) else None
-                lp = st.get('lazy_prod')              # the activation under the head was never stored: recomputed from z
+        kind = st['kind']
+        sg = st.get('src_grad')
+        if sg is not None:
+            for gap in sg['gaps']:
+                ops.fill_zero(self.gview(gap))
+        if kind == 'head':
+            conv = st['conv']
+            k = conv.out_channels
+            assert sg is None or not sg['accumulate']
+            fused = bool(st.get('dgrad_fused'))     # the data gradient is formed by the BatchNorm backward of the layer below
+            dsrc = self.gview(st['src']) if (sg is not None and not fused) else None
+            lp = st.get('lazy_prod')              # the activation under the head was never stored: recomputed from z
 
-                def wgrad_only():
-                    if lp is not None:
-                        ops.head1x1_wgrad_bn(dlogits, lp['z'], lp['scale'], lp['shift'], gslot(conv.weight).view(k, -1),
-                                             gslot(conv.bias), ws=self.head_ws)
-                    else:
-                        ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), None,
-                                        gslot(conv.weight).view(k, -1), gslot(conv.bias), ws=self.head_ws)
-                if side is not None and sg is not None:
-                    # the head's weight gradient (one pass over the widest feature map) has no consumer until the
-                    # optimizer: side stream, so that the dependent chain starts with the data gradient alone
-                    with ops.use_stream(side):
-                        wgrad_only()
-                    if dsrc is not None:
-                        ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc, None, None,
-                                        ws=self.head_ws)
-                elif lp is not None:
-                    wgrad_only()
-                    if dsrc is not None:
-                        ops.head1x1_bwd(dlogits, lp['z'], conv.weight.view(k, -1), dsrc, None, None, ws=self.head_ws)
+            def wgrad_only():
+                if lp is not None:
+                    ops.head1x1_wgrad_bn(dlogits, lp['z'], lp['scale'], lp['shift'], gslot(conv.weight).view(k, -1),
+                                         gslot(conv.bias), ws=self.head_ws)
                 else:
-                    ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc,
+                    ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), None,
                                     gslot(conv.weight).view(k, -1), gslot(conv.bias), ws=self.head_ws)
-            elif kind in ('conv', 'convT'):
-                conv, bn = st['conv'], st['bn']
-                z = st['z']
-                dz = st['dz']
-                # a layer that hands its dz over to the weight-gradient stream right away: the event rides on the
-                # BatchNorm backward's last dispatch (done=) and the other stream only waits for it -- no record packet
-                # between this launch and the data-gradient convolution on this queue
-                tail_ = self.cfg.tail_wgrad_main and st is self.steps[0] and sg is None and self.profiler is None
-                done = st['ev'] if (side is not None and not tail_ and self.cfg.handover_on_kernel) else None
-                if st.get('head_fuse') is not None and not folded[0]:
-                    hconv = st['head_fuse']['conv']
-                    ops.bn_relu_bwd_head(dlogits, hconv.weight.view(hconv.out_channels, -1), z, dz, st['mean'], st['rstd'], st['scale'],
-                                         st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
-                elif st.get('pool_fuse') is not None and not folded[0]:
-                    # (its activation was max-pooled: the pooled gradient joins dA inside this kernel, no pooling backward pass)
-                    ops.bn_relu_bwd_pool(self.gview(st['dst']), self.gview(st['pool_fuse']), z, dz, st['mean'], st['rstd'],
-                                         st['scale'], st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws,
-                                         True, done=done)
-                elif folded[0]:                  # dA is still in the split-K slabs of the conv after this one
-                    ops.bn_relu_bwd_slabs(sk_ws, folded[0], z, dz, st['mean'], st['rstd'], st['scale'], st['shift'],
-                                          gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
-                    folded[0] = 0
-                else:
-                    ops.bn_relu_bwd(self.gview(st['dst']), z, dz, st['mean'], st['rstd'], st['scale'],
-                                    st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias),
-                                    bn_ws, True, done=done)
-                x = self.view(st['src'], inputs)
-                if kind == 'conv':
-                    prof = self.profiler
-                    wq = self._wq_active
-                    wfn = (ops.conv3x3_wgrad_bf16 if st['wino_w'] == BF16 else
-                           (lambda d_, x_, w_, ws=None, queue=None: ops.conv3x3_wgrad_wino4(d_, x_, w_, ws=ws, target_wgs=256,
-                                                                                            queue=queue))
-                           if st.get('wg_target') else
-                           ops.conv3x3_wgrad_wino4 if st['wino_w'] == 4 else
-                           ops.conv3x3_wgrad_wino if st['wino_w'] else ops.conv3x3_wgrad)
-                    wgrad = lambda d_, x_, w_, ws=None: wfn(d_, x_, w_, ws=ws, queue=wq)
-                    # the last op of the pass, when it has no data gradient (a stem conv): the dependent chain ends with its
-                    # BatchNorm backward, so its weight gradient runs on that stream beside whatever the weight-gradient
-                    # stream still has queued instead of behind it
-                    tail = self.cfg.tail_wgrad_main and st is self.steps[0] and sg is None and prof is None
-                    if side is not None and not tail:
-                        if done is not None:
-                            ops.wait(side, done)
-                        else:
-                            ops.order(st['ev'], main, side)
-                        with ops.use_stream(side):
-                            if prof is not None:
-                                prof.begin(WGRAD_TAG[st['wino_w']], st['flops'], st['flops'] * EXEC_FRAC[st['wino_w']])
-                            wgrad(dz, x, gslot(conv.weight), ws=st['wg_ws'])
-                            if prof is not None:
-                                prof.end()
-                    else:
-                        if prof is not None:
-                            prof.begin(WGRAD_TAG[st['wino_w']], st['flops'], st['flops'] * EXEC_FRAC[st['wino_w']])
-                        if tail and side is not None:
-                            # (tail) its slabs are reduced right behind it on this stream (queue = None): handing them to the
-                            # final batched launch of the weight-gradient stream would put two stream hand-overs and that
-                            # launch between this kernel and the optimizer (C2 +0.3 %, C4 +0.25 %, C5 +0.15 % same box)
-                            wfn(dz, x, gslot(conv.weight), ws=st['wg_ws'], queue=None)
-                        else:
-                            wgrad(dz, x, gslot(conv.weight), ws=st['wg_ws'])
-                        if prof is not None:
-                            prof.end()
-                    if sg is not None:
-                        if prof is not None:
-                            prof.begin(FWD_TAG[st['wino_d']], st['flops'], st['flops'] * EXEC_FRAC[st['wino_d']])
-                        if st['wino_d'] == BF16:
-                            ops.conv3x3_bf16(dz, st['ud'], None, self.gview(st['src']),
-                                             accumulate=sg['accumulate'], splitk=st['plan_d'] >> 8, ws=sk_ws)
-                        elif st['wino_d'] == 4:
-                            ops.conv3x3_wino4(dz, st['ud'], None, self.gview(st['src']),
-                                              accumulate=2 if st['fold_dgrad'] else sg['accumulate'],
-                                              splitk=st['plan_d'] >> 8, ws=sk_ws)
-                        elif st['wino_d']:
-                            ops.conv3x3_wino(dz, st['ud'], None, self.gview(st['src']),
-                                             accumulate=2 if st['fold_dgrad'] else sg['accumulate'],
-                                             splitk=st['plan_d'] >> 8, ws=sk_ws)
-                        else:
-                            ops.conv3x3_igemm(dz, st['wd'], None, self.gview(st['src']),
-                                              accumulate=sg['accumulate'], plan=st['plan_d'], ws=sk_ws)
-                        if prof is not None:
-                            prof.end()
-                        if st['fold_dgrad']:
-                            folded[0] = st['plan_d'] >> 8
-                else:
-                    # the last op of the pass, when it has no data gradient (a stem conv): the dependent chain ends with its
-                    # BatchNorm backward, so its weight gradient runs on that stream beside whatever the weight-gradient
-                    # stream still has queued instead of behind it
-                    tail = self.cfg.tail_wgrad_main and st is self.steps[0] and sg is None and prof is None
-                    if side is not None and not tail:
-                        if done is not None:
-                            ops.wait(side, done)
-                        else:
-                            ops.order(st['ev'], main, side)
-                        with ops.use_stream(side):
-                            ops.convT2x2_wgrad(x, dz, gslot(conv.weight), ws=st['wg_ws'])
-                    else:
-                        ops.convT2x2_wgrad(x, dz, gslot(conv.weight), ws=st['wg_ws'])
-                    if sg is not None:
-                        ops.convT2x2_dgrad(dz, conv.weight, self.gview(st['src']))
-            elif kind == 'sa':
-                m = st['mod']
-                y, dout = self.view(st['src'], inputs), self.gview(st['dst'])
-                dil = m.conv2.dilation[0]
-                shp = st['t1'].shape
-                da, db = self.sa_da[:st['t1'].numel()].view(shp), self.sa_db[:st['t1'].numel()].view(shp)
-                mnum = st['gate'].numel()
-                dt4 = self.sa_ws[mnum + 8:mnum + 8 + mnum].view(st['t4'].shape)
-                ops.sa_gate_bwd(dout, y, st['gate'], st['t4'], st['stat'], m.bn.weight, gslot(m.bn.weight),
-                                gslot(m.bn.bias), dt4, self.sa_ws[:mnum + 4])
-                ops.pwconv_wgrad(dt4, st['t3'], gslot(m.conv4.weight), gslot(m.conv4.bias))
-                ops.pwconv_dgrad(dt4, m.conv4.weight, da)                                  # da = d t3
-                ops.dconv_small_wgrad(da, st['t2'], gslot(m.conv3.weight), gslot(m.conv3.bias), dil)
-                ops.dconv_small(da, m.conv3.weight, None, db, dil, transposed=True)       # db = d t2
-                ops.dconv_small_wgrad(db, st['t1'], gslot(m.conv2.weight), gslot(m.conv2.bias), dil)
-                ops.dconv_small(db, m.conv2.weight, None, da, dil, transposed=True)       # da = d t1
-                ops.pwconv_wgrad(da, y, gslot(m.conv1.weight), gslot(m.conv1.bias))
-                # d y = gate * dout (the multiply) + conv1^T d t1, in one pass over the C channels
-                ops.pwconv_dgrad(da, m.conv1.weight, self.gview(st['src']), gate=st['gate'], dout=dout,
-                                 accumulate=sg['accumulate'])
-            elif kind == 'pool':
-                if sg is not None and not st.get('bwd_fused'):
-                    ops.maxpool2x2_bwd(self.view(st['src'], inputs), self.gview(st['dst']),
-                                       self.gview(st['src']), accumulate=sg['accumulate'])
-            elif kind == 'up':
+            if side is not None and sg is not None:
+                # the head's weight gradient (one pass over the widest feature map) has no consumer until the
+                # optimizer: side stream, so that the dependent chain starts with the data gradient alone
+                with ops.use_stream(side):
+                    wgrad_only()
+                if dsrc is not None:
+                    ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc, None, None,
+                                    ws=self.head_ws)
+            elif lp is not None:
+                wgrad_only()
+                if dsrc is not None:
+                    ops.head1x1_bwd(dlogits, lp['z'], conv.weight.view(k, -1), dsrc, None, None, ws=self.head_ws)
+            else:
+                ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc,
+                                gslot(conv.weight).view(k, -1), gslot(conv.bias), ws=self.head_ws)
+        elif kind in ('conv', 'convT'):
+            conv, bn = st['conv'], st['bn']
+            z = st['z']
+            dz = st['dz']
+            prof = self.profiler
+            # the last op of the pass, when it has no data gradient (a stem conv): the dependent chain ends with its
+            # BatchNorm backward, so its weight gradient runs on that stream beside whatever the weight-gradient
+            # stream still has queued instead of behind it
+            tail = self.cfg.tail_wgrad_main and st is self.steps[0] and sg is None and prof is None
+            # a layer that hands its dz over to the weight-gradient stream right away: the event rides on the
+            # BatchNorm backward's last dispatch (done=) and the other stream only waits for it -- no record packet
+            # between this launch and the data-gradient convolution on this queue
+            done = st['ev'] if (side is not None and not tail and self.cfg.handover_on_kernel) else None
+            if st.get('head_fuse') is not None and not folded[0]:
+                hconv = st['head_fuse']['conv']
+                ops.bn_relu_bwd_head(dlogits, hconv.weight.view(hconv.out_channels, -1), z, dz, st['mean'], st['rstd'], st['scale'],
+                                     st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
+            elif st.get('pool_fuse') is not None and not folded[0]:
+                # (its activation was max-pooled: the pooled gradient joins dA inside this kernel, no pooling backward pass)
+                ops.bn_relu_bwd_pool(self.gview(st['dst']), self.gview(st['pool_fuse']), z, dz, st['mean'], st['rstd'],
+                                     st['scale'], st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws,
+                                     True, done=done)
+            elif folded[0]:                  # dA is still in the split-K slabs of the conv after this one
+                ops.bn_relu_bwd_slabs(sk_ws, folded[0], z, dz, st['mean'], st['rstd'], st['scale'], st['shift'],
+                                      gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
+                folded[0] = 0
+            else:
+                ops.bn_relu_bwd(self.gview(st['dst']), z, dz, st['mean'], st['rstd'], st['scale'],
+                                st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias),
+                                bn_ws, True, done=done)
+            x = self.view(st['src'], inputs)
+            if kind == 'conv':
+                fam_w = FAMILIES[st['wino_w']]
+                # (tail) its slabs are reduced right behind it on this stream (queue = None): handing them to the
+                # final batched launch of the weight-gradient stream would put two stream hand-overs and that
+                # launch between this kernel and the optimizer (C2 +0.3 %, C4 +0.25 %, C5 +0.15 % same box)
+                wq = None if (tail and side is not None) else self._wq_active
+
+                def wgrad():
+                    if prof is not None:
+                        prof.begin(fam_w.wgrad_tag, st['flops'], st['flops'] * fam_w.exec_frac)
+                    fam_w.wgrad(dz, x, gslot(conv.weight), ws=st['wg_ws'], queue=wq, **_wgrad_extra(st))
+                    if prof is not None:
+                        prof.end()
+                self._wgrad_handover(st, wgrad, tail, done, main, side)
                 if sg is not None:
-                    ops.upsample2x_bwd(self.gview(st['dst']), self.gview(st['src']),
-                                       accumulate=sg['accumulate'])
+                    fam_d = FAMILIES[st['wino_d']]
+                    if prof is not None:
+                        prof.begin(fam_d.fwd_tag, st['flops'], st['flops'] * fam_d.exec_frac)
+                    # (fold_dgrad: the split-K slabs stay for the BatchNorm backward before this layer -- Winograd launches only)
+                    assert not st['fold_dgrad'] or fam_d.mode in (2, 4)
+                    fam_d.conv(dz, st[_pack_slot(fam_d.mode, 'd')], None, self.gview(st['src']),
+                               accumulate=2 if st['fold_dgrad'] else sg['accumulate'], plan=st['plan_d'], ws=sk_ws)
+                    if prof is not None:
+                        prof.end()
+                    if st['fold_dgrad']:
+                        folded[0] = st['plan_d'] >> 8
+            else:
+                self._wgrad_handover(st, lambda: ops.convT2x2_wgrad(x, dz, gslot(conv.weight), ws=st['wg_ws']), tail, done,
+                                     main, side)
+                if sg is not None:
+                    ops.convT2x2_dgrad(dz, conv.weight, self.gview(st['src']))
+        elif kind == 'sa':
+            m = st['mod']
+            y, dout = self.view(st['src'], inputs), self.gview(st['dst'])
+            dil = m.conv2.dilation[0]
+            shp = st['t1'].shape
+            da, db = self.sa_da[:st['t1'].numel()].view(shp), self.sa_db[:st['t1'].numel()].view(shp)
+            mnum = st['gate'].numel()
+            dt4 = self.sa_ws[mnum + 8:mnum + 8 + mnum].view(st['t4'].shape)
+            ops.sa_gate_bwd(dout, y, st['gate'], st['t4'], st['stat'], m.bn.weight, gslot(m.bn.weight),
+                            gslot(m.bn.bias), dt4, self.sa_ws[:mnum + 4])
+            ops.pwconv_wgrad(dt4, st['t3'], gslot(m.conv4.weight), gslot(m.conv4.bias))
+            ops.pwconv_dgrad(dt4, m.conv4.weight, da)                                  # da = d t3
+            ops.dconv_small_wgrad(da, st['t2'], gslot(m.conv3.weight), gslot(m.conv3.bias), dil)
+            ops.dconv_small(da, m.conv3.weight, None, db, dil, transposed=True)       # db = d t2
+            ops.dconv_small_wgrad(db, st['t1'], gslot(m.conv2.weight), gslot(m.conv2.bias), dil)
+            ops.dconv_small(db, m.conv2.weight, None, da, dil, transposed=True)       # da = d t1
+            ops.pwconv_wgrad(da, y, gslot(m.conv1.weight), gslot(m.conv1.bias))
+            # d y = gate * dout (the multiply) + conv1^T d t1, in one pass over the C channels
+            ops.pwconv_dgrad(da, m.conv1.weight, self.gview(st['src']), gate=st['gate'], dout=dout,
+                             accumulate=sg['accumulate'])
+        elif kind == 'pool':
+            if sg is not None and not st.get('bwd_fused'):
+                ops.maxpool2x2_bwd(self.view(st['src'], inputs), self.gview(st['dst']),
+                                   self.gview(st['src']), accumulate=sg['accumulate'])
+        elif kind == 'up':
+            if sg is not None:
+                ops.upsample2x_bwd(self.gview(st['dst']), self.gview(st['src']),
+                                   accumulate=sg['accumulate'])
 
 
 

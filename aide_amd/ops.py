@@ -4,7 +4,9 @@ PyTorch is used here only for device memory and the current HIP stream; every fu
 launches hand-written gfx950 kernels from libaide_hip.so and nothing else. Inputs must live on a
 HIP device: there is no CPU path.
 """
+import collections
 import ctypes
+import struct
 
 import torch
 
@@ -135,6 +137,9 @@ def ptr(t):
 
 
 # ------------------------------------------------------------------------------- conv 3x3
+BF16 = 16                      # conv mode id of the bf16-MFMA kernels (conv3x3_bf16.hip); the others: FAMILIES below
+
+
 def conv_chunk(cin):
     return lib.aide_conv3x3_chunk(cin)
 
@@ -147,27 +152,15 @@ def pack_weights(w, need_dgrad=True):
     """w [Co,Ci,3,3] -> (wf [ci_pad,9,Co], wd [co_pad,9,Ci] | None)."""
     _req(w)
     co, ci = w.shape[0], w.shape[1]
-    ci_pad, co_pad = pad_to(ci, conv_chunk(ci)), pad_to(co, conv_chunk(co))
-    wf = torch.empty(ci_pad, 9, co, device=w.device, dtype=torch.float32)
-    wd = torch.empty(co_pad, 9, ci, device=w.device, dtype=torch.float32) if need_dgrad else None
-    check(lib.aide_conv3x3_pack_weights(ptr(w), ptr(wf), ptr(wd), co, ci, ci_pad, co_pad, stream_ptr()),
-          'conv3x3_pack_weights')
+    wf = FAMILIES[0].pack_alloc(ci, co, w.device)
+    wd = FAMILIES[0].pack_alloc(co, ci, w.device) if need_dgrad else None
+    pack_weights_into(w, wf, wd)
     return wf, wd
 
 
 def pack_table(entries, device):
-    """entries: list of (w, wf|None, wd|None) -> (device table, n, total_blocks) for
-    aide_conv3x3_pack_weights_multi (48-byte records, see include/aide_hip.h)."""
-    import struct
-    rec, start = b'', 0
-    for w, wf, wd in entries:
-        co, ci = w.shape[0], w.shape[1]
-        elems = (wf.numel() if wf is not None else 0) + (wd.numel() if wd is not None else 0)
-        rec += struct.pack('<QQQiiiiq', w.data_ptr(), wf.data_ptr() if wf is not None else 0,
-                           wd.data_ptr() if wd is not None else 0, co, ci,
-                           wf.shape[0] if wf is not None else 0, wd.shape[0] if wd is not None else 0, start)
-        start += (elems + 255) // 256
-    return torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(device), len(entries), start
+    """entries: list of (w, wf|None, wd|None) -> (device table, n, total_blocks) for aide_conv3x3_pack_weights_multi."""
+    return _pack_table(FAMILIES[0], entries, device)
 
 
 def pack_weights_into(w, wf, wd):
@@ -526,38 +519,21 @@ def wino_supported(cin, h, w, cout):
 
 def wino_pack_table(entries, device):
     """entries: list of (w, uf, ud|None). -> (device table, n, total_blocks) for aide_conv3x3_wino_pack_multi."""
-    import struct
-    rec, start = b'', 0
-    for w, uf, ud in entries:
-        co, ci = w.shape[0], w.shape[1]
-        rec += struct.pack('<QQQiiiiq', w.data_ptr(), uf.data_ptr() if uf is not None else 0,
-                           ud.data_ptr() if ud is not None else 0, co, ci,
-                           uf.shape[0] if uf is not None else 0, ud.shape[0] if ud is not None else 0, start)
-        start += lib.aide_conv3x3_wino_pack_blocks(co, ci)
-    return torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(device), len(entries), start
+    return _pack_table(FAMILIES[2], entries, device)
 
 
 def wino_pack(w, need_dgrad=True):
     """w [Co,Ci,3,3] -> (uf [ci_pad,16,Co], ud [co_pad,16,Ci] | None): G g G^T of the (rotated) filters."""
-    _req(w)
-    co, ci = w.shape[0], w.shape[1]
-    uf = torch.empty(pad_to(ci, 8), 16, co, device=w.device, dtype=torch.float32)
-    ud = torch.empty(pad_to(co, 8), 16, ci, device=w.device, dtype=torch.float32) if need_dgrad else None
-    tab, n, blocks = wino_pack_table([(w, uf, ud)], w.device)
-    check(lib.aide_conv3x3_wino_pack_multi(ptr(tab), n, blocks, stream_ptr()), 'conv3x3_wino_pack_multi')
-    return uf, ud
+    return _pack_one(FAMILIES[2], w, need_dgrad)
 
 
-def conv3x3_wino(x, u, bias, y, accumulate=False, splitk=-1, ws=None):
+def conv3x3_wino(x, u, bias, y, accumulate=False, splitk=-1, ws=None, plan=None):
     xp, xbs = planes(x)
     yp, ybs = planes(y)
     n, cin, h, w = x.shape
     cout = y.shape[1]
     assert u.shape[1] == 16 and u.shape[2] == cout and u.shape[0] >= cin
-    if splitk < 0:
-        splitk = lib.aide_conv3x3_wino_splitk(n, cin, h, w, cout)
-    if splitk > 1 and ws is None:
-        ws = torch.empty(lib.aide_conv3x3_ws_bytes(n, h, w, cout, splitk) // 4, device=x.device, dtype=torch.float32)
+    splitk, ws = _splitk_ws(FAMILIES[2], x, cout, splitk, plan, ws)
     check(lib.aide_conv3x3_wino(xp, xbs, ptr(u), ptr(bias), yp, ybs, n, cin, h, w, cout, int(accumulate), splitk,
                                 ptr(ws), stream_ptr()), 'conv3x3_wino')
     return y
@@ -570,29 +546,16 @@ def wino4_supported(cin, h, w, cout):
 
 def wino4_pack_table(entries, device):
     """entries: list of (w, uf|None, ud|None). -> (device table, n, total_blocks) for aide_conv3x3_wino4_pack_multi."""
-    import struct
-    rec, start = b'', 0
-    for w, uf, ud in entries:
-        co, ci = w.shape[0], w.shape[1]
-        rec += struct.pack('<QQQiiiiq', w.data_ptr(), uf.data_ptr() if uf is not None else 0,
-                           ud.data_ptr() if ud is not None else 0, co, ci, 0, 0, start)
-        start += lib.aide_conv3x3_wino4_pack_blocks(co, ci)
-    return torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(device), len(entries), start
+    return _pack_table(FAMILIES[4], entries, device)
 
 
 def wino4_pack(w, need_dgrad=True):
     """w [Co,Ci,3,3] -> (uf [Ci,36,Co], ud [Co,36,Ci] | None): 6x6 G g G^T of the (rotated) filters, channel-blocked by 4."""
-    _req(w)
-    co, ci = w.shape[0], w.shape[1]
-    uf = torch.empty(ci, 36, co, device=w.device, dtype=torch.float32)
-    ud = torch.empty(co, 36, ci, device=w.device, dtype=torch.float32) if need_dgrad else None
-    tab, n, blocks = wino4_pack_table([(w, uf, ud)], w.device)
-    check(lib.aide_conv3x3_wino4_pack_multi(ptr(tab), n, blocks, stream_ptr()), 'conv3x3_wino4_pack_multi')
-    return uf, ud
+    return _pack_one(FAMILIES[4], w, need_dgrad)
 
 
 def conv3x3_wino4(x, u, bias, y, accumulate=False, splitk=-1, ws=None, stats=None, epi_scale=None, epi_relu=True,
-                  in_tab=None, in_group_images=0):
+                  in_tab=None, in_group_images=0, plan=None):
     """stats [cout * wino4_stats_parts * 2]: the launch also writes its BatchNorm statistics partials (non-split,
     accumulate = 0, W >= 32); epi_scale [cout]: y = relu?(acc * epi_scale + bias) (eval-mode BatchNorm folded in);
     in_tab [n / in_group_images, cin, 2]: x is the raw output of the layer before, the loader applies relu(x * scale + shift)"""
@@ -601,10 +564,7 @@ def conv3x3_wino4(x, u, bias, y, accumulate=False, splitk=-1, ws=None, stats=Non
     n, cin, h, w = x.shape
     cout = y.shape[1]
     assert u.shape[1] == 36 and u.shape[2] == cout and u.shape[0] == cin
-    if splitk < 0:
-        splitk = lib.aide_conv3x3_wino4_splitk(n, cin, h, w, cout)
-    if splitk > 1 and ws is None:
-        ws = torch.empty(lib.aide_conv3x3_ws_bytes(n, h, w, cout, splitk) // 4, device=x.device, dtype=torch.float32)
+    splitk, ws = _splitk_ws(FAMILIES[4], x, cout, splitk, plan, ws)
     check(lib.aide_conv3x3_wino4(xp, xbs, ptr(u), ptr(bias), yp, ybs, n, cin, h, w, cout, int(accumulate), splitk,
                                  ptr(ws), ptr(stats), ptr(epi_scale), int(bool(epi_relu)), ptr(in_tab), int(in_group_images),
                                  stream_ptr()), 'conv3x3_wino4')
@@ -623,28 +583,15 @@ def bf16_pack_alloc(cout, cin, device):
 
 def bf16_pack_table(entries, device):
     """entries: list of (w, uf|None, ud|None) -> (device table, n, total_blocks) for aide_conv3x3_bf16_pack_multi."""
-    import struct
-    rec, start = b'', 0
-    for w, uf, ud in entries:
-        co, ci = w.shape[0], w.shape[1]
-        rec += struct.pack('<QQQiiiiq', w.data_ptr(), uf.data_ptr() if uf is not None else 0,
-                           ud.data_ptr() if ud is not None else 0, co, ci, 0, 0, start)
-        start += lib.aide_conv3x3_bf16_pack_blocks(co, ci)
-    return torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(device), len(entries), start
+    return _pack_table(FAMILIES[BF16], entries, device)
 
 
 def bf16_pack(w, need_dgrad=True):
     """w [Co,Ci,3,3] fp32 -> (uf, ud | None) bf16 packs (RNE)."""
-    _req(w)
-    co, ci = w.shape[0], w.shape[1]
-    uf = bf16_pack_alloc(co, ci, w.device)
-    ud = bf16_pack_alloc(ci, co, w.device) if need_dgrad else None
-    tab, n, blocks = bf16_pack_table([(w, uf, ud)], w.device)
-    check(lib.aide_conv3x3_bf16_pack_multi(ptr(tab), n, blocks, stream_ptr()), 'conv3x3_bf16_pack_multi')
-    return uf, ud
+    return _pack_one(FAMILIES[BF16], w, need_dgrad)
 
 
-def conv3x3_bf16(x, u, bias, y, accumulate=False, splitk=-1, ws=None):
+def conv3x3_bf16(x, u, bias, y, accumulate=False, splitk=-1, ws=None, plan=None):
     """y (+)= conv3x3(x) on the bf16 MFMA path (bf16 operands, fp32 accumulation).  x, y are fp32 tensors; y may be a
     bf16-stored z (forward) or x a bf16-stored dz (dgrad)."""
     xp, xbs = planes(x, bf16_ok=True)
@@ -652,10 +599,7 @@ def conv3x3_bf16(x, u, bias, y, accumulate=False, splitk=-1, ws=None):
     n, cin, h, w = x.shape
     cout = y.shape[1]
     assert u.dtype == torch.int16 and u.numel() == lib.aide_conv3x3_bf16_pack_elems(cout, cin)
-    if splitk < 0:
-        splitk = lib.aide_conv3x3_bf16_splitk(n, cin, h, w, cout)
-    if splitk > 1 and ws is None:
-        ws = torch.empty(lib.aide_conv3x3_ws_bytes(n, h, w, cout, splitk) // 4, device=x.device, dtype=torch.float32)
+    splitk, ws = _splitk_ws(FAMILIES[BF16], x, cout, splitk, plan, ws)
     check(lib.aide_conv3x3_bf16_mixed(xp, int(is_bf16(x)), xbs, ptr(u), ptr(bias), yp, int(is_bf16(y)), ybs, n, cin, h,
                                       w, cout, int(accumulate), splitk, ptr(ws), stream_ptr()), 'conv3x3_bf16')
     return y
@@ -718,6 +662,109 @@ def conv3x3_wgrad_wino(dz, a, dw, ws=None, queue=None):
     check(lib.aide_conv3x3_wgrad_wino(dp, dbs, ap, abs_, ptr(dw), n, co, ci, h, w, ptr(ws), _qh(queue), stream_ptr()),
           'conv3x3_wgrad_wino')
     return dw
+
+
+# ------------------------------------------------------------------------------- the 3x3-conv kernel families
+# One record per kernel family of the 3x3 convolution: everything the engine needs to know to pick it, size its buffers,
+# refresh its filter packs and launch it in the three directions.  The engine walks this table (engine.select_conv, Plan);
+# adding, changing or retiring a family is an edit HERE (and of its kernels), nowhere else.
+#   mode                       the id plans store per layer and direction (st['wino_f' | 'wino_d' | 'wino_w'])
+#   fwd_tag, wgrad_tag         profiler tags = the kernel that does the work of one conv operator call (its split reduce
+#                              rides along); bench.py's roofline block keys on them
+#   exec_frac                  multiplies a launch executes per algorithmic (direct-convolution) multiply
+#   supported(cin, h, w, cout), wgrad_supported(co, ci, h, w)
+#   plan(n, cin, h, w, cout)   variant | splitk << 8 (the direct kernel has variants; the others: splitk << 8)
+#   pack_alloc(cin, cout, device)   uninitialised filter pack of one direction ((cout, cin): the dgrad direction)
+#   pack_blocks(co, ci, uf, ud)     workgroups one entry of a pack table occupies in the *_pack_multi launch
+#   pack_padded                the record's two row-count fields carry the packs' padded channel counts
+#   pack_multi                 name of the *_pack_multi entry point (without aide_)
+#   conv(x, pack, bias, y, accumulate=, plan=, ws=, ...)     forward / data-gradient launcher
+#   wgrad(dz, a, dw, ws=, queue=, ...), wgrad_ws_bytes(n, co, ci, h, w, ...)
+ConvFamily = collections.namedtuple('ConvFamily', 'mode fwd_tag wgrad_tag exec_frac supported wgrad_supported plan pack_alloc '
+                                    'pack_blocks pack_padded pack_multi conv wgrad wgrad_ws_bytes')
+
+
+def _f32_pack(rows, taps):
+    return lambda cin, cout, device: torch.empty(rows(cin), taps, cout, device=device, dtype=torch.float32)
+
+
+FAMILIES = {
+    0: ConvFamily(                                                       # direct implicit GEMM
+        0, 'conv3x3_mfma_kernel', 'conv3x3_wgrad_kernel', 1.0,
+        supported=lambda cin, h, w, cout: True, wgrad_supported=lambda co, ci, h, w: True,
+        plan=lambda n, cin, h, w, cout: lib.aide_conv3x3_plan(n, cin, h, w, cout),
+        pack_alloc=_f32_pack(lambda cin: pad_to(cin, conv_chunk(cin)), 9),
+        pack_blocks=lambda co, ci, uf, ud: (sum(t.numel() for t in (uf, ud) if t is not None) + 255) // 256,
+        pack_padded=True, pack_multi='conv3x3_pack_weights_multi', conv=conv3x3_igemm, wgrad=conv3x3_wgrad,
+        wgrad_ws_bytes=lambda n, co, ci, h, w: lib.aide_conv3x3_wgrad_ws_bytes(n, co, ci, h, w)),
+    2: ConvFamily(                                                       # Winograd F(2x2,3x3)
+        2, 'conv3x3_wino_kernel', 'conv3x3_wgrad_wino_kernel', 16.0 / 36.0,
+        supported=wino_supported, wgrad_supported=wgrad_wino_supported,
+        plan=lambda n, cin, h, w, cout: lib.aide_conv3x3_wino_splitk(n, cin, h, w, cout) << 8,
+        pack_alloc=_f32_pack(lambda cin: pad_to(cin, 8), 16),
+        pack_blocks=lambda co, ci, uf, ud: lib.aide_conv3x3_wino_pack_blocks(co, ci),
+        pack_padded=True, pack_multi='conv3x3_wino_pack_multi', conv=conv3x3_wino, wgrad=conv3x3_wgrad_wino,
+        wgrad_ws_bytes=lambda n, co, ci, h, w: lib.aide_conv3x3_wgrad_wino_ws_bytes(n, co, ci, h, w)),
+    4: ConvFamily(                                                       # Winograd F(4x4,3x3)
+        4, 'conv3x3_wino4_kernel', 'conv3x3_wgrad4_kernel', 36.0 / 144.0,
+        supported=wino4_supported, wgrad_supported=wgrad_wino4_supported,
+        plan=lambda n, cin, h, w, cout: lib.aide_conv3x3_wino4_splitk(n, cin, h, w, cout) << 8,
+        pack_alloc=_f32_pack(lambda cin: cin, 36),
+        pack_blocks=lambda co, ci, uf, ud: lib.aide_conv3x3_wino4_pack_blocks(co, ci),
+        pack_padded=False, pack_multi='conv3x3_wino4_pack_multi', conv=conv3x3_wino4, wgrad=conv3x3_wgrad_wino4,
+        wgrad_ws_bytes=lambda n, co, ci, h, w, target_wgs=0:
+            lib.aide_conv3x3_wgrad_wino4_ws_bytes_t(n, co, ci, h, w, target_wgs)),
+    BF16: ConvFamily(                                                    # bf16 MFMA
+        BF16, 'conv3x3_bf16_kernel', 'conv3x3_wgrad_bf16_kernel', 1.0,
+        supported=bf16_supported, wgrad_supported=wgrad_bf16_supported,
+        plan=lambda n, cin, h, w, cout: lib.aide_conv3x3_bf16_splitk(n, cin, h, w, cout) << 8,
+        pack_alloc=lambda cin, cout, device: bf16_pack_alloc(cout, cin, device),
+        pack_blocks=lambda co, ci, uf, ud: lib.aide_conv3x3_bf16_pack_blocks(co, ci),
+        pack_padded=False, pack_multi='conv3x3_bf16_pack_multi', conv=conv3x3_bf16, wgrad=conv3x3_wgrad_bf16,
+        wgrad_ws_bytes=lambda n, co, ci, h, w, co_blocks=0:
+            lib.aide_conv3x3_wgrad_bf16_ws_bytes(n, co, ci, h, w, co_blocks)),
+}
+
+
+def _splitk_ws(fam, x, cout, splitk, plan, ws):
+    """-> (split count, split-K workspace) of a launch of `fam`: the split count of `plan` (plan >> 8) if one is given, else
+    `splitk`, else (< 0) the library's rule; the workspace is allocated when the launch splits and the caller brought none"""
+    n, cin, h, w = x.shape
+    if plan is not None:
+        splitk = plan >> 8
+    elif splitk < 0:
+        splitk = fam.plan(n, cin, h, w, cout) >> 8
+    if splitk > 1 and ws is None:
+        ws = torch.empty(lib.aide_conv3x3_ws_bytes(n, h, w, cout, splitk) // 4, device=x.device, dtype=torch.float32)
+    return splitk, ws
+
+
+def _pack_table(fam, entries, device):
+    """entries: list of (w [Co,Ci,3,3], uf|None, ud|None) -> (device table, n, total_blocks) for fam's *_pack_multi launch:
+    48-byte records {w, uf, ud, Co, Ci, rows of uf, rows of ud, first block} (see include/aide_hip.h)"""
+    rec, start = b'', 0
+    for w, uf, ud in entries:
+        co, ci = w.shape[0], w.shape[1]
+        rows = [t.shape[0] if (fam.pack_padded and t is not None) else 0 for t in (uf, ud)]
+        rec += struct.pack('<QQQiiiiq', w.data_ptr(), uf.data_ptr() if uf is not None else 0,
+                           ud.data_ptr() if ud is not None else 0, co, ci, rows[0], rows[1], start)
+        start += fam.pack_blocks(co, ci, uf, ud)
+    return torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(device), len(entries), start
+
+
+def launch_pack_multi(fam, tab):
+    """launch fam's filter re-layout over a table of _pack_table"""
+    check(getattr(lib, 'aide_' + fam.pack_multi)(ptr(tab[0]), tab[1], tab[2], stream_ptr()), fam.pack_multi)
+
+
+def _pack_one(fam, w, need_dgrad):
+    """w [Co,Ci,3,3] -> freshly allocated (forward pack, dgrad pack | None) of `fam`"""
+    _req(w)
+    co, ci = w.shape[0], w.shape[1]
+    uf = fam.pack_alloc(ci, co, w.device)
+    ud = fam.pack_alloc(co, ci, w.device) if need_dgrad else None
+    launch_pack_multi(fam, _pack_table(fam, [(w, uf, ud)], w.device))
+    return uf, ud
 
 
 # ------------------------------------------------------------------------------- Spatial_Attention branch
