@@ -900,6 +900,17 @@ int pick_splits(int N, int C, int HW) {
     return s;
 }
 
+// ---- dispatch from run-time values to kernel instantiations: written once here, used by every launcher below
+// storage flag of an untyped pointer -> f(aide_type<float | bf16_t>{})
+template <class F> auto with_storage(int bf16, F&& f) { return aide_with_storage<bf16_t>(bf16 != 0, f); }
+// the one-pass instantiation of a CoopPlan: launch(V, Q) as integral constants.  Vs...: the unit widths the call site's kernel
+// exists for -- {8, 4}, or {8} for the pool kernels, whose callers reject every other plan
+template <int... Vs, class F> void coop_launch(const CoopPlan& cp, F&& launch) {
+    aide_pick<Vs...>(cp.V, [&](auto v) { aide_pick<1, 2, 4, 8>(cp.Q, [&](auto q) { launch(v, q); }); });
+}
+// the two-pass fallback: pair(V) launches its (reduce, apply) kernels with V = 8 / 4 / 1 values per lane
+template <class F> void two_pass_launch(bool v8, bool v4, F&& pair) { aide_pick<8, 4, 1>(v8 ? 8 : v4 ? 4 : 1, pair); }
+
 }  // namespace
 
 extern "C" {
@@ -914,7 +925,8 @@ namespace {
 
 // N: images per group; groups > 1: a stacked batch of `groups` runs of N images, each with its own batch statistics, the
 // running statistics updated once per group in order (one launch sequence instead of `groups`)
-template <typename ZT, typename AT, bool SLABS = false>
+// (SLABS first, ZT / AT deduced from the pointers: the slab-fed callers write bn_train_fwd_t<true>(...))
+template <bool SLABS = false, typename ZT, typename AT>
 int bn_train_fwd_t(const ZT* z, int64_t z_bs, AT* a, int64_t a_bs, int N, int C, int H, int W,
                    const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
                    float* running_var, long long* num_batches_tracked, float* mean, float* rstd,
@@ -928,48 +940,38 @@ int bn_train_fwd_t(const ZT* z, int64_t z_bs, AT* a, int64_t a_bs, int N, int C,
     if ((long)groups * splits > 96) return AIDE_ERR_ARG;
     double* partials = (double*)ws;
     const double count = (double)N * HW;
-    const int gx = max(1, min((HW / (v4 ? 4 : 1) + 255) / 256, 16));
     const int NT = N * groups;
     // algorithmic bytes of the layer (kernel timer): the input read once (z, or the slabs + the z it writes), a written once
     const double kt_bytes = (double)NT * C * HW * ((SLABS ? 4.0 * sl.splitk : 0.0) + sizeof(ZT) + sizeof(AT));
     // one pass, S workgroups per channel (all BASELINE shapes); the two-pass kernels below remain for planes that are not a
     // multiple of 4 values and for channels beyond BN_MAX_S * 2048 units
-    {
-        CoopPlan cp;
-        constexpr bool narrow = !(std::is_same<ZT, float>::value && std::is_same<AT, float>::value);
-        if (v4 && coop_plan(N, C, HW, z_bs % 8 == 0 && a_bs % 8 == 0 && (!SLABS || sl.split_stride % 8 == 0), cp, narrow)) {
-#define AIDE_BN_FC(VV, QQ)                                                                                                    \
-            AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_fwd_coop_kernel<VV, QQ, ZT, AT, SLABS>), dim3(C * cp.S), dim3(256), 0, stream, z, \
-                               (long)z_bs, a, (long)a_bs, N, C, HW, cp.S, cp.per, count, gamma, beta, eps, momentum,          \
-                               running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift, relu, sl, groups,    \
-                               (double*)ws, PoolSrc{})
-#define AIDE_BN_FQ(VV) do { if (cp.Q == 1) AIDE_BN_FC(VV, 1); else if (cp.Q == 2) AIDE_BN_FC(VV, 2); else if (cp.Q == 4) AIDE_BN_FC(VV, 4); else AIDE_BN_FC(VV, 8); } while (0)
-            if (cp.V == 8) AIDE_BN_FQ(8); else AIDE_BN_FQ(4);
-#undef AIDE_BN_FQ
-#undef AIDE_BN_FC
-            return aide_launch_status();
-        }
+    CoopPlan cp;
+    constexpr bool narrow = !(std::is_same<ZT, float>::value && std::is_same<AT, float>::value);
+    if (v4 && coop_plan(N, C, HW, z_bs % 8 == 0 && a_bs % 8 == 0 && (!SLABS || sl.split_stride % 8 == 0), cp, narrow)) {
+        coop_launch<8, 4>(cp, [&](auto v, auto q) {
+            AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_fwd_coop_kernel<v(), q(), ZT, AT, SLABS>),
+                              dim3(C * cp.S), dim3(256), 0, stream, z, (long)z_bs, a, (long)a_bs, N, C, HW, cp.S, cp.per, count, gamma,
+                              beta, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift, relu, sl,
+                              groups, (double*)ws, PoolSrc{});
+        });
+        return aide_launch_status();
     }
     // 8 values per lane: 16-byte accesses for the bf16-stored tensors of the precision='bf16' mode
     // (for every storage type: the bf16-storage kernels stay bit-identical to the fp32-storage ones on the widened tensor)
     const bool v8 = v4 && !SLABS && HW % 8 == 0 && z_bs % 8 == 0 && a_bs % 8 == 0;
-    if (v8) {
-        const int gx8 = max(1, min((HW / 8 + 255) / 256, 16));
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, 0.0, (bn_stats_kernel<8, ZT, false>), dim3(C * splits, groups), dim3(256), 0, stream, z, (long)z_bs, N, C, HW, splits, partials, sl);
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_train_apply_kernel<8, ZT, AT>), dim3(NT * C, gx8), dim3(256), 0, stream, z, (long)z_bs, a, (long)a_bs, C, HW,
-                           partials, splits, count, gamma, beta, eps, momentum, running_mean, running_var,
-                           num_batches_tracked, mean, rstd, scale, shift, relu, (const float*)nullptr, 0, (const float*)nullptr, 0, N, groups);
-    } else if (v4) {
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, 0.0, (bn_stats_kernel<4, ZT, SLABS>), dim3(C * splits, groups), dim3(256), 0, stream, z, (long)z_bs, N, C, HW, splits, partials, sl);
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_train_apply_kernel<4, ZT, AT>), dim3(NT * C, gx), dim3(256), 0, stream, z, (long)z_bs, a, (long)a_bs, C, HW,
-                           partials, splits, count, gamma, beta, eps, momentum, running_mean, running_var,
-                           num_batches_tracked, mean, rstd, scale, shift, relu, (const float*)nullptr, 0, (const float*)nullptr, 0, N, groups);
-    } else {
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, 0.0, (bn_stats_kernel<1, ZT, false>), dim3(C * splits, groups), dim3(256), 0, stream, z, (long)z_bs, N, C, HW, splits, partials, sl);
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_train_apply_kernel<1, ZT, AT>), dim3(NT * C, gx), dim3(256), 0, stream, z, (long)z_bs, a, (long)a_bs, C, HW,
-                           partials, splits, count, gamma, beta, eps, momentum, running_mean, running_var,
-                           num_batches_tracked, mean, rstd, scale, shift, relu, (const float*)nullptr, 0, (const float*)nullptr, 0, N, groups);
-    }
+    two_pass_launch(v8, v4, [&](auto v) {
+        constexpr int V = v();
+        // slabs reach the two-pass kernels at width 4 only (v4 is required above, v8 excludes them): the statistics kernel
+        // exists with SLABS for V = 4 alone, and naming <8 | 1, ZT, true> here would instantiate two kernels nothing launches
+        constexpr bool STATS_SLABS = SLABS && V == 4;
+        const int gx = max(1, min((HW / V + 255) / 256, 16));
+        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, 0.0, (bn_stats_kernel<V, ZT, STATS_SLABS>), dim3(C * splits, groups), dim3(256), 0, stream,
+                          z, (long)z_bs, N, C, HW, splits, partials, sl);
+        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_train_apply_kernel<V, ZT, AT>), dim3(NT * C, gx), dim3(256), 0, stream, z,
+                          (long)z_bs, a, (long)a_bs, C, HW, partials, splits, count, gamma, beta, eps, momentum, running_mean,
+                          running_var, num_batches_tracked, mean, rstd, scale, shift, relu, (const float*)nullptr, 0,
+                          (const float*)nullptr, 0, N, groups);
+    });
     return aide_launch_status();
 }
 
@@ -996,32 +998,25 @@ int bn_relu_bwd_t(const GT* dA, int64_t d_bs, const ZT* z, int64_t z_bs, DT* dz,
     double* partials = (double*)ws;
     const double count = (double)N * HW;
     const double kt_bytes = (double)N * C * HW * (sizeof(GT) + sizeof(ZT) + sizeof(DT));     // dA, z read once, dz written once
-    {
-        CoopPlan cp;
-        constexpr bool narrow = !(std::is_same<ZT, float>::value && std::is_same<DT, float>::value && std::is_same<GT, float>::value);
-        if (v4 && coop_plan(N, C, HW, z_bs % 8 == 0 && d_bs % 8 == 0 && dz_bs % 8 == 0, cp, narrow)) {
-#define AIDE_BN_BC(VV, QQ)                                                                                                    \
-            AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_coop_kernel<VV, QQ, ZT, DT, GT, false>), dim3(C * cp.S), dim3(256), 0, \
-                             stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S, cp.per, count, mean,     \
-                             rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, PoolSrc{})
-#define AIDE_BN_BQ(VV) do { if (cp.Q == 1) AIDE_BN_BC(VV, 1); else if (cp.Q == 2) AIDE_BN_BC(VV, 2); else if (cp.Q == 4) AIDE_BN_BC(VV, 4); else AIDE_BN_BC(VV, 8); } while (0)
-            if (cp.V == 8) AIDE_BN_BQ(8); else AIDE_BN_BQ(4);
-#undef AIDE_BN_BQ
-#undef AIDE_BN_BC
-            return aide_launch_status();
-        }
+    CoopPlan cp;
+    constexpr bool narrow = !(std::is_same<ZT, float>::value && std::is_same<DT, float>::value && std::is_same<GT, float>::value);
+    if (v4 && coop_plan(N, C, HW, z_bs % 8 == 0 && d_bs % 8 == 0 && dz_bs % 8 == 0, cp, narrow)) {
+        coop_launch<8, 4>(cp, [&](auto v, auto q) {
+            AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_coop_kernel<v(), q(), ZT, DT, GT, false>),
+                                   dim3(C * cp.S), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S,
+                                   cp.per, count, mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, PoolSrc{});
+        });
+        return aide_launch_status();
     }
     const bool v8 = v4 && HW % 8 == 0 && z_bs % 8 == 0 && d_bs % 8 == 0 && dz_bs % 8 == 0;
-    if (v8) {
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_BWD, 0.0, (bn_bwd_reduce_kernel<8, ZT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, N, C, HW, splits, mean, rstd, scale, shift, relu, partials);
-        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_apply_kernel<8, ZT, DT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, splits, count, mean, rstd, scale, shift, relu, partials, dgamma, dbeta, dbias);
-    } else if (v4) {
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_BWD, 0.0, (bn_bwd_reduce_kernel<4, ZT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, N, C, HW, splits, mean, rstd, scale, shift, relu, partials);
-        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_apply_kernel<4, ZT, DT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, splits, count, mean, rstd, scale, shift, relu, partials, dgamma, dbeta, dbias);
-    } else {
-        AIDE_LAUNCH_TIMED(AIDE_KT_BN_BWD, 0.0, (bn_bwd_reduce_kernel<1, ZT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, N, C, HW, splits, mean, rstd, scale, shift, relu, partials);
-        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_apply_kernel<1, ZT, DT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, splits, count, mean, rstd, scale, shift, relu, partials, dgamma, dbeta, dbias);
-    }
+    two_pass_launch(v8, v4, [&](auto v) {
+        constexpr int V = v();
+        AIDE_LAUNCH_TIMED(AIDE_KT_BN_BWD, 0.0, (bn_bwd_reduce_kernel<V, ZT, GT>), dim3(C * splits), dim3(256), 0, stream, dA, (long)d_bs,
+                          z, (long)z_bs, N, C, HW, splits, mean, rstd, scale, shift, relu, partials);
+        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_apply_kernel<V, ZT, DT, GT>), dim3(C * splits), dim3(256), 0, stream,
+                               dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, splits, count, mean, rstd, scale, shift, relu,
+                               partials, dgamma, dbeta, dbias);
+    });
     return aide_launch_status();
 }
 
@@ -1037,12 +1032,10 @@ int aide_bn_train_fwd_mixed(const void* z, int z_bf16, int64_t z_bs, void* a, in
                             int H, int W, const float* gamma, const float* beta, float eps, float momentum,
                             float* running_mean, float* running_var, long long* num_batches_tracked, float* mean,
                             float* rstd, float* scale, float* shift, int relu, void* ws, hipStream_t stream) {
-#define AIDE_BN_FWD(ZT, AT) bn_train_fwd_t<ZT, AT>((const ZT*)z, z_bs, (AT*)a, a_bs, N, C, H, W, gamma, beta, eps, momentum, \
-                                                   running_mean, running_var, num_batches_tracked, mean, rstd, scale,      \
-                                                   shift, relu, ws, stream)
-    if (z_bf16) return a_bf16 ? AIDE_BN_FWD(bf16_t, bf16_t) : AIDE_BN_FWD(bf16_t, float);
-    return a_bf16 ? AIDE_BN_FWD(float, bf16_t) : AIDE_BN_FWD(float, float);
-#undef AIDE_BN_FWD
+    return with_storage(z_bf16, [&](auto zt) { return with_storage(a_bf16, [&](auto at) {
+        return bn_train_fwd_t(zt.cast(z), z_bs, at.cast(a), a_bs, N, C, H, W, gamma, beta, eps, momentum, running_mean, running_var,
+                              num_batches_tracked, mean, rstd, scale, shift, relu, ws, stream);
+    }); });
 }
 
 // The same operator fed by the split-K slabs of the convolution before it (launched with accumulate = 2): sums
@@ -1055,12 +1048,10 @@ int aide_bn_train_fwd_slabs(const float* slabs, int splitk, int64_t split_stride
                             float* shift, int relu, void* ws, hipStream_t stream) {
     SlabSrc sl;
     sl.slabs = slabs; sl.bias = bias; sl.split_stride = split_stride; sl.slab_bs = (long)C * H * W; sl.splitk = splitk;
-#define AIDE_BN_FWD_S(ZT, AT) bn_train_fwd_t<ZT, AT, true>((const ZT*)z, z_bs, (AT*)a, a_bs, N, C, H, W, gamma, beta, eps,   \
-                                                           momentum, running_mean, running_var, num_batches_tracked, mean, \
-                                                           rstd, scale, shift, relu, ws, stream, sl)
-    if (z_bf16) return a_bf16 ? AIDE_BN_FWD_S(bf16_t, bf16_t) : AIDE_BN_FWD_S(bf16_t, float);
-    return a_bf16 ? AIDE_BN_FWD_S(float, bf16_t) : AIDE_BN_FWD_S(float, float);
-#undef AIDE_BN_FWD_S
+    return with_storage(z_bf16, [&](auto zt) { return with_storage(a_bf16, [&](auto at) {
+        return bn_train_fwd_t<true>(zt.cast(z), z_bs, at.cast(a), a_bs, N, C, H, W, gamma, beta, eps, momentum, running_mean, running_var,
+                                    num_batches_tracked, mean, rstd, scale, shift, relu, ws, stream, sl);
+    }); });
 }
 
 // N images per group, `groups` groups stacked along the batch; group g's entries are parts[c][g * nparts .. (g + 1) * nparts)
@@ -1074,13 +1065,14 @@ static int bn_parts_launch(const void* z, int z_bf16, int64_t z_bs, void* a, int
         return AIDE_ERR_ARG;
     const double count = (double)N * HW;
     const int gx = max(1, min((HW / 4 + 255) / 256, 16));
-#define AIDE_BN_PARTS(ZT, AT)                                                                                                  \
-    AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, (double)N * groups * C * HW * (sizeof(ZT) + sizeof(AT)), (bn_train_apply_kernel<4, ZT, AT>), dim3(N * groups * C, gx), dim3(256), 0, stream, (const ZT*)z, (long)z_bs, \
-                       (AT*)a, (long)a_bs, C, HW, (const double*)nullptr, 0, count, gamma, beta, eps, momentum, running_mean, \
-                       running_var, num_batches_tracked, mean, rstd, scale, shift, relu, parts, nparts, conv_bias, parts_stride, N, groups)
-    if (z_bf16) { if (a_bf16) AIDE_BN_PARTS(bf16_t, bf16_t); else AIDE_BN_PARTS(bf16_t, float); }
-    else { if (a_bf16) AIDE_BN_PARTS(float, bf16_t); else AIDE_BN_PARTS(float, float); }
-#undef AIDE_BN_PARTS
+    with_storage(z_bf16, [&](auto zt) { with_storage(a_bf16, [&](auto at) {
+        using ZT = typename decltype(zt)::type;
+        using AT = typename decltype(at)::type;
+        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, (double)N * groups * C * HW * (sizeof(ZT) + sizeof(AT)), (bn_train_apply_kernel<4, ZT, AT>),
+                          dim3(N * groups * C, gx), dim3(256), 0, stream, zt.cast(z), (long)z_bs, at.cast(a), (long)a_bs, C, HW,
+                          (const double*)nullptr, 0, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
+                          mean, rstd, scale, shift, relu, parts, nparts, conv_bias, parts_stride, N, groups);
+    }); });
     return aide_launch_status();
 }
 
@@ -1089,12 +1081,6 @@ static int bn_parts_launch(const void* z, int z_bf16, int64_t z_bs, void* a, int
 // read of z.  (H*W % 4 == 0 and 16-byte aligned batch strides.)
 // parts_stride: entries per channel in `parts` (>= nparts).  A group of a stacked batch passes the pointer to ITS first
 // entry of channel 0 and the count of its own entries (the conv writes the entries of an image contiguously).
-int aide_bn_train_fwd_parts_strided(const void* z, int z_bf16, int64_t z_bs, void* a, int a_bf16, int64_t a_bs, int N, int C,
-                                    int H, int W, const float* parts, int nparts, int parts_stride, const float* conv_bias,
-                                    const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                                    float* running_var, long long* num_batches_tracked, float* mean, float* rstd,
-                                    float* scale, float* shift, int relu, hipStream_t stream);
-
 int aide_bn_train_fwd_parts_strided(const void* z, int z_bf16, int64_t z_bs, void* a, int a_bf16, int64_t a_bs, int N, int C,
                                     int H, int W, const float* parts, int nparts, int parts_stride, const float* conv_bias,
                                     const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
@@ -1155,35 +1141,29 @@ int aide_bn_train_fwd_groups(const void* z, int z_bf16, int64_t z_bs, void* a, i
                                shift, relu, stream);
     SlabSrc sl = SlabSrc{};
     if (slabs) { sl.slabs = slabs; sl.bias = slab_bias; sl.split_stride = split_stride; sl.slab_bs = (long)C * H * W; sl.splitk = splitk; }
-#define AIDE_BN_FWD_G(ZT, AT)                                                                                                  \
-    (slabs ? bn_train_fwd_t<ZT, AT, true>((const ZT*)z, z_bs, (AT*)a, a_bs, N, C, H, W, gamma, beta, eps, momentum, running_mean, \
-                                          running_var, num_batches_tracked, mean, rstd, scale, shift, relu, ws, stream, sl, groups) \
-           : bn_train_fwd_t<ZT, AT, false>((const ZT*)z, z_bs, (AT*)a, a_bs, N, C, H, W, gamma, beta, eps, momentum, running_mean, \
-                                           running_var, num_batches_tracked, mean, rstd, scale, shift, relu, ws, stream, sl, groups))
-    if (z_bf16) return a_bf16 ? AIDE_BN_FWD_G(bf16_t, bf16_t) : AIDE_BN_FWD_G(bf16_t, float);
-    return a_bf16 ? AIDE_BN_FWD_G(float, bf16_t) : AIDE_BN_FWD_G(float, float);
-#undef AIDE_BN_FWD_G
+    return with_storage(z_bf16, [&](auto zt) { return with_storage(a_bf16, [&](auto at) {
+        return aide_pick<1, 0>(slabs != nullptr, [&](auto fed) {
+            return bn_train_fwd_t<fed() != 0>(zt.cast(z), z_bs, at.cast(a), a_bs, N, C, H, W, gamma, beta, eps, momentum, running_mean,
+                                              running_var, num_batches_tracked, mean, rstd, scale, shift, relu, ws, stream, sl, groups);
+        });
+    }); });
 }
 
 int aide_bn_relu_apply_mixed(const void* z, int z_bf16, int64_t z_bs, void* a, int a_bf16, int64_t a_bs, int N, int C,
                              int H, int W, const float* scale, const float* shift, int relu, hipStream_t stream) {
-#define AIDE_BN_APPLY(ZT, AT) bn_relu_apply_t<ZT, AT>((const ZT*)z, z_bs, (AT*)a, a_bs, N, C, H, W, scale, shift, relu, stream)
-    if (z_bf16) return a_bf16 ? AIDE_BN_APPLY(bf16_t, bf16_t) : AIDE_BN_APPLY(bf16_t, float);
-    return a_bf16 ? AIDE_BN_APPLY(float, bf16_t) : AIDE_BN_APPLY(float, float);
-#undef AIDE_BN_APPLY
+    return with_storage(z_bf16, [&](auto zt) { return with_storage(a_bf16, [&](auto at) {
+        return bn_relu_apply_t(zt.cast(z), z_bs, at.cast(a), a_bs, N, C, H, W, scale, shift, relu, stream);
+    }); });
 }
 
 int aide_bn_relu_bwd_mixed(const void* dA, int dA_bf16, int64_t d_bs, const void* z, int z_bf16, int64_t z_bs, void* dz,
                            int dz_bf16, int64_t dz_bs, int N, int C, int H, int W, const float* mean, const float* rstd,
                            const float* scale, const float* shift, int relu, float* dgamma, float* dbeta, float* dbias,
                            void* ws, void* done, hipStream_t stream) {
-#define AIDE_BN_BWD(ZT, DT, GT) bn_relu_bwd_t<ZT, DT, GT>((const GT*)dA, d_bs, (const ZT*)z, z_bs, (DT*)dz, dz_bs, N, C, H, W, \
-                                                          mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, ws, done, stream)
-#define AIDE_BN_BWD_G(ZT, DT) (dA_bf16 ? AIDE_BN_BWD(ZT, DT, bf16_t) : AIDE_BN_BWD(ZT, DT, float))
-    if (z_bf16) return dz_bf16 ? AIDE_BN_BWD_G(bf16_t, bf16_t) : AIDE_BN_BWD_G(bf16_t, float);
-    return dz_bf16 ? AIDE_BN_BWD_G(float, bf16_t) : AIDE_BN_BWD_G(float, float);
-#undef AIDE_BN_BWD_G
-#undef AIDE_BN_BWD
+    return with_storage(z_bf16, [&](auto zt) { return with_storage(dz_bf16, [&](auto dt) { return with_storage(dA_bf16, [&](auto gt) {
+        return bn_relu_bwd_t(gt.cast(dA), d_bs, zt.cast(z), z_bs, dt.cast(dz), dz_bs, N, C, H, W, mean, rstd, scale, shift, relu, dgamma,
+                             dbeta, dbias, ws, done, stream);
+    }); }); });
 }
 
 // Backward of relu(bn(z)) with dA taken from the split-K slabs [splitk][N][C][H][W] of the data-gradient convolution that
@@ -1199,14 +1179,12 @@ int aide_bn_relu_bwd_slabs(const float* slabs, int splitk, int64_t split_stride,
         return AIDE_ERR_ARG;
     SlabSrc sl;
     sl.slabs = slabs; sl.bias = nullptr; sl.split_stride = split_stride; sl.slab_bs = (long)C * HW; sl.splitk = splitk;
-#define AIDE_BN_BS(VV, QQ)                                                                                                    \
-    AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, (double)N * C * HW * (4.0 * splitk + 8.0), done, (bn_bwd_coop_kernel<VV, QQ, float, float, float, true>), dim3(C * cp.S), dim3(256), 0, stream, \
-                     (const float*)nullptr, 0L, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S, cp.per, (double)N * HW, mean, \
-                     rstd, scale, shift, relu, dgamma, dbeta, dbias, sl, (double*)ws, PoolSrc{})
-#define AIDE_BN_BQ(VV) do { if (cp.Q == 1) AIDE_BN_BS(VV, 1); else if (cp.Q == 2) AIDE_BN_BS(VV, 2); else if (cp.Q == 4) AIDE_BN_BS(VV, 4); else AIDE_BN_BS(VV, 8); } while (0)
-    if (cp.V == 8) AIDE_BN_BQ(8); else AIDE_BN_BQ(4);
-#undef AIDE_BN_BQ
-#undef AIDE_BN_BS
+    coop_launch<8, 4>(cp, [&](auto v, auto q) {
+        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, (double)N * C * HW * (4.0 * splitk + 8.0), done,
+                               (bn_bwd_coop_kernel<v(), q(), float, float, float, true>), dim3(C * cp.S),
+                               dim3(256), 0, stream, (const float*)nullptr, 0L, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S, cp.per,
+                               (double)N * HW, mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, sl, (double*)ws, PoolSrc{});
+    });
     return aide_launch_status();
 }
 
@@ -1225,12 +1203,12 @@ int aide_bn_train_fwd_pool(const float* z, int64_t z_bs, float* a, int64_t a_bs,
     PoolSrc pl;
     pl.pdy = pooled; pl.pdy_bs = pooled_bs; pl.W = W; pl.hw = nullptr; pl.K = 0;
     const double kt_bytes = (double)N * groups * C * HW * 9.0;      // z in, a out, a quarter of it once more
-#define AIDE_BN_FP(QQ)                                                                                                        \
-    AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_fwd_coop_kernel<8, QQ, float, float, false, true>), dim3(C * cp.S), dim3(256), 0,   \
-                      stream, z, (long)z_bs, a, (long)a_bs, N, C, HW, cp.S, cp.per, (double)N * HW, gamma, beta, eps, momentum,          \
-                      running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift, relu, SlabSrc{}, groups, (double*)ws, pl)
-    if (cp.Q == 1) AIDE_BN_FP(1); else if (cp.Q == 2) AIDE_BN_FP(2); else if (cp.Q == 4) AIDE_BN_FP(4); else AIDE_BN_FP(8);
-#undef AIDE_BN_FP
+    coop_launch<8>(cp, [&](auto v, auto q) {
+        AIDE_LAUNCH_TIMED(AIDE_KT_BN_FWD, kt_bytes, (bn_fwd_coop_kernel<v(), q(), float, float, false, true>),
+                          dim3(C * cp.S), dim3(256), 0, stream, z, (long)z_bs, a, (long)a_bs, N, C, HW, cp.S, cp.per, (double)N * HW, gamma,
+                          beta, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift, relu, SlabSrc{},
+                          groups, (double*)ws, pl);
+    });
     return aide_launch_status();
 }
 
@@ -1255,12 +1233,12 @@ int aide_bn_relu_bwd_pool(const float* dA, int64_t d_bs, const float* pdy, int64
     pl.pdy = pdy; pl.pdy_bs = pdy_bs; pl.W = W; pl.hw = nullptr; pl.K = 0;
     // dA, z read once, dz written once, the pooled gradient read once (the partner rows of z come from cache)
     const double kt_bytes = (double)N * C * HW * 12.0 + (double)N * C * (HW / 4) * 4.0;
-#define AIDE_BN_BP(QQ)                                                                                                        \
-    AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_coop_kernel<8, QQ, float, float, float, false, true>),     \
-                           dim3(C * cp.S), dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S, \
-                           cp.per, (double)N * HW, mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, pl)
-    if (cp.Q == 1) AIDE_BN_BP(1); else if (cp.Q == 2) AIDE_BN_BP(2); else if (cp.Q == 4) AIDE_BN_BP(4); else AIDE_BN_BP(8);
-#undef AIDE_BN_BP
+    coop_launch<8>(cp, [&](auto v, auto q) {
+        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done,
+                               (bn_bwd_coop_kernel<v(), q(), float, float, float, false, true>), dim3(C * cp.S),
+                               dim3(256), 0, stream, dA, (long)d_bs, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, cp.S, cp.per, (double)N * HW,
+                               mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, pl);
+    });
     return aide_launch_status();
 }
 
@@ -1279,14 +1257,12 @@ int aide_bn_relu_bwd_head(const float* dlogits, int64_t dl_bs, const float* head
     PoolSrc pl;
     pl.pdy = dlogits; pl.pdy_bs = dl_bs; pl.W = W; pl.hw = head_w; pl.K = K;
     const double kt_bytes = (double)N * C * HW * 8.0 + (double)N * K * HW * 4.0;       // z, dz; dlogits once (re-read from cache per channel)
-#define AIDE_BN_BH(VV, QQ)                                                                                                    \
-    AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done, (bn_bwd_coop_kernel<VV, QQ, float, float, float, false, false, true>), \
-                           dim3(C * cp.S), dim3(256), 0, stream, (const float*)nullptr, 0L, z, (long)z_bs, dz, (long)dz_bs, N, C, HW, \
-                           cp.S, cp.per, (double)N * HW, mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, pl)
-#define AIDE_BN_BQ(VV) do { if (cp.Q == 1) AIDE_BN_BH(VV, 1); else if (cp.Q == 2) AIDE_BN_BH(VV, 2); else if (cp.Q == 4) AIDE_BN_BH(VV, 4); else AIDE_BN_BH(VV, 8); } while (0)
-    if (cp.V == 8) AIDE_BN_BQ(8); else AIDE_BN_BQ(4);
-#undef AIDE_BN_BQ
-#undef AIDE_BN_BH
+    coop_launch<8, 4>(cp, [&](auto v, auto q) {
+        AIDE_LAUNCH_DONE_TIMED(AIDE_KT_BN_BWD, kt_bytes, done,
+                               (bn_bwd_coop_kernel<v(), q(), float, float, float, false, false, true>),
+                               dim3(C * cp.S), dim3(256), 0, stream, (const float*)nullptr, 0L, z, (long)z_bs, dz, (long)dz_bs, N, C, HW,
+                               cp.S, cp.per, (double)N * HW, mean, rstd, scale, shift, relu, dgamma, dbeta, dbias, SlabSrc{}, (double*)ws, pl);
+    });
     return aide_launch_status();
 }
 

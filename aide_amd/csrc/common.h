@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -127,6 +128,26 @@ extern "C" int aide_ktimer_slot(int family, double work, hipStream_t stream, hip
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                      \
     } while (0)
 #define AIDE_CONV_FLOPS(N, H, W, Co, Ci) (2.0 * (double)(N) * (double)(H) * (double)(W) * (double)(Co) * (double)(Ci) * 9.0)
+
+// ---- host-side dispatch from run-time values to template arguments: each ladder is written once, here, and a launcher passes
+// a generic lambda that names its kernel and calls the launch macros above.  Only what a lambda names is instantiated.
+// Storage type behind an untyped pointer: f(aide_type<float>{}) or, bf16-stored, f(aide_type<BF>{}) with the calling file's
+// 16-bit type BF; tag.cast(p) types the pointer.  Nest the calls for two or three operands.
+template <typename T> struct aide_type {
+    using type = T;
+    static T* cast(void* p) { return static_cast<T*>(p); }
+    static const T* cast(const void* p) { return static_cast<const T*>(p); }
+};
+template <typename BF, class F> auto aide_with_storage(bool bf16, F&& f) {
+    if (bf16) return f(aide_type<BF>{});
+    return f(aide_type<float>{});
+}
+// Compile-time constant: f(std::integral_constant<int, V>{}) for the V of Vs... that equals v.  Any other v takes the LAST of
+// Vs..., as the `else` / `default:` of the ladders this replaces did (Q: not 1, 2, 4 -> 8; V: not 8 -> 4; K: not 1..7 -> 8).
+template <int V0, int... Vs, class F> auto aide_pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else { if (v == V0) return f(std::integral_constant<int, V0>{}); return aide_pick<Vs...>(v, f); }
+}
 
 // XCD-aware bijective remap of a 1-D block id: the hardware dispatches block b to XCD b % 8;
 // give every XCD a contiguous range of logical tiles so neighbouring tiles (shared halo rows,

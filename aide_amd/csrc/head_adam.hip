@@ -215,10 +215,10 @@ int head_fwd_t(const XT* x, int64_t x_bs, const float* w, const float* b, float*
     const long total4 = (long)N * HW / 4;
     const int grid = grid_for(total4);
     const size_t sh = (size_t)K * C * sizeof(float);
-#define AIDE_HEAD_FWD(KK) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (head_fwd_kernel<KK, XT>), dim3(grid), dim3(256), sh, stream, x, (long)x_bs, w, b, y, (long)y_bs, C, HW, total4, in_scale, in_shift)
-    switch (K) { case 1: AIDE_HEAD_FWD(1); break; case 2: AIDE_HEAD_FWD(2); break; case 3: AIDE_HEAD_FWD(3); break; case 4: AIDE_HEAD_FWD(4); break;
-                 case 5: AIDE_HEAD_FWD(5); break; case 6: AIDE_HEAD_FWD(6); break; case 7: AIDE_HEAD_FWD(7); break; default: AIDE_HEAD_FWD(8); }
-#undef AIDE_HEAD_FWD
+    aide_pick<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto k) {
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (head_fwd_kernel<k(), XT>), dim3(grid), dim3(256), sh, stream, x, (long)x_bs, w, b, y,
+                          (long)y_bs, C, HW, total4, in_scale, in_shift);
+    });
     return aide_launch_status();
 }
 
@@ -232,24 +232,16 @@ int head_bwd_t(const float* dy, int64_t dy_bs, const XT* x, int64_t x_bs, const 
     const size_t sh = (size_t)K * C * sizeof(float);
     if (dx) {
         const int grid = grid_for(total4);
-#define AIDE_HEAD_DG(KK) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (head_dgrad_kernel<KK, DT>), dim3(grid), dim3(256), sh, stream, dy, (long)dy_bs, w, dx, (long)dx_bs, C, HW, total4)
-        switch (K) { case 1: AIDE_HEAD_DG(1); break; case 2: AIDE_HEAD_DG(2); break; case 3: AIDE_HEAD_DG(3); break; case 4: AIDE_HEAD_DG(4); break;
-                     case 5: AIDE_HEAD_DG(5); break; case 6: AIDE_HEAD_DG(6); break; case 7: AIDE_HEAD_DG(7); break; default: AIDE_HEAD_DG(8); }
-#undef AIDE_HEAD_DG
+        aide_pick<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto k) {
+            AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (head_dgrad_kernel<k(), DT>), dim3(grid), dim3(256), sh, stream, dy, (long)dy_bs, w, dx,
+                              (long)dx_bs, C, HW, total4);
+        });
     }
     if (!dw) return aide_launch_status();      // data gradient only (the weight gradient is issued on another stream)
     const int nblocks = (int)max(1L, min((total4 + 255) / 256, (long)HEAD_WG_BLOCKS));
-    int rc;
-    switch (K) {
-        case 1: rc = head_wgrad_launch<1>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 2: rc = head_wgrad_launch<2>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 3: rc = head_wgrad_launch<3>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 4: rc = head_wgrad_launch<4>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 5: rc = head_wgrad_launch<5>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 6: rc = head_wgrad_launch<6>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        case 7: rc = head_wgrad_launch<7>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift); break;
-        default: rc = head_wgrad_launch<8>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift);
-    }
+    const int rc = aide_pick<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto k) {
+        return head_wgrad_launch<k()>(dy, dy_bs, x, x_bs, C, HW, total4, (double*)ws, nblocks, stream, in_scale, in_shift);
+    });
     if (rc) return rc;
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, head_wgrad_finalize_kernel, dim3(K * C + K), dim3(64), 0, stream,
                        (const double*)ws, nblocks, K * C, K, dw, db);
@@ -266,16 +258,14 @@ size_t aide_head1x1_ws_bytes(int C, int K) { return (size_t)HEAD_WG_BLOCKS * (K 
 // the head on a bf16-stored feature map (precision='bf16'); logits and every gradient stay fp32
 int aide_head1x1_fwd_mixed(const void* x, int x_bf16, int64_t x_bs, const float* w, const float* b, float* y,
                            int64_t y_bs, int N, int C, int K, int H, int W, hipStream_t stream) {
-    return x_bf16 ? head_fwd_t((const bf16_store_t*)x, x_bs, w, b, y, y_bs, N, C, K, H, W, stream)
-                  : head_fwd_t((const float*)x, x_bs, w, b, y, y_bs, N, C, K, H, W, stream);
+    return aide_with_storage<bf16_store_t>(x_bf16, [&](auto xt) { return head_fwd_t(xt.cast(x), x_bs, w, b, y, y_bs, N, C, K, H, W, stream); });
 }
 int aide_head1x1_bwd_mixed(const float* dy, int64_t dy_bs, const void* x, int x_bf16, int64_t x_bs, const float* w,
                            void* dx, int dx_bf16, int64_t dx_bs, float* dw, float* db, int N, int C, int K, int H, int W,
                            void* ws, hipStream_t stream) {
-#define AIDE_HB(XT, DT) head_bwd_t(dy, dy_bs, (const XT*)x, x_bs, w, (DT*)dx, dx_bs, dw, db, N, C, K, H, W, ws, stream)
-    if (x_bf16) return dx_bf16 ? AIDE_HB(bf16_store_t, bf16_store_t) : AIDE_HB(bf16_store_t, float);
-    return dx_bf16 ? AIDE_HB(float, bf16_store_t) : AIDE_HB(float, float);
-#undef AIDE_HB
+    return aide_with_storage<bf16_store_t>(x_bf16, [&](auto xt) { return aide_with_storage<bf16_store_t>(dx_bf16, [&](auto dt) {
+        return head_bwd_t(dy, dy_bs, xt.cast(x), x_bs, w, dt.cast(dx), dx_bs, dw, db, N, C, K, H, W, ws, stream);
+    }); });
 }
 
 // The head on the RAW conv output z of the layer under it, that layer's training-mode BatchNorm + ReLU applied on the way in

@@ -619,10 +619,9 @@ int aide_maxpool2x2_fwd(const float* x, int64_t x_bs, float* y, int64_t y_bs, in
 int aide_maxpool2x2_fwd_mixed(const void* x, int x_bf16, int64_t x_bs, void* y, int y_bf16, int64_t y_bs, int N, int C,
                               int H, int W, hipStream_t stream) {
     if (H % 2 || W % 4 || x_bs % 4 || y_bs % 2) return AIDE_ERR_ARG;
-    if (x_bf16) return y_bf16 ? maxpool_fwd_t((const bf16_store_t*)x, x_bs, (bf16_store_t*)y, y_bs, N, C, H, W, stream)
-                              : maxpool_fwd_t((const bf16_store_t*)x, x_bs, (float*)y, y_bs, N, C, H, W, stream);
-    return y_bf16 ? maxpool_fwd_t((const float*)x, x_bs, (bf16_store_t*)y, y_bs, N, C, H, W, stream)
-                  : maxpool_fwd_t((const float*)x, x_bs, (float*)y, y_bs, N, C, H, W, stream);
+    return aide_with_storage<bf16_store_t>(x_bf16, [&](auto xt) { return aide_with_storage<bf16_store_t>(y_bf16, [&](auto yt) {
+        return maxpool_fwd_t(xt.cast(x), x_bs, yt.cast(y), y_bs, N, C, H, W, stream);
+    }); });
 }
 
 int aide_maxpool2x2_bwd(const float* x, int64_t x_bs, const float* dy, int64_t dy_bs, float* dx,
@@ -640,12 +639,11 @@ int aide_maxpool2x2_bwd(const float* x, int64_t x_bs, const float* dy, int64_t d
 int aide_maxpool2x2_bwd_mixed(const void* x, int x_bf16, int64_t x_bs, const void* dy, int dy_bf16, int64_t dy_bs, void* dx,
                               int dx_bf16, int64_t dx_bs, int N, int C, int H, int W, int accumulate, hipStream_t stream) {
     if (H % 2 || W % 4 || x_bs % 4 || dx_bs % 4 || dy_bs % 2) return AIDE_ERR_ARG;
-#define AIDE_PB(XT, GT, DT) maxpool_bwd_t((const XT*)x, x_bs, (const GT*)dy, dy_bs, (DT*)dx, dx_bs, N, C, H, W, accumulate, stream)
-#define AIDE_PB_X(GT, DT) (x_bf16 ? AIDE_PB(bf16_store_t, GT, DT) : AIDE_PB(float, GT, DT))
-    if (dy_bf16) return dx_bf16 ? AIDE_PB_X(bf16_store_t, bf16_store_t) : AIDE_PB_X(bf16_store_t, float);
-    return dx_bf16 ? AIDE_PB_X(float, bf16_store_t) : AIDE_PB_X(float, float);
-#undef AIDE_PB_X
-#undef AIDE_PB
+    return aide_with_storage<bf16_store_t>(dy_bf16, [&](auto gt) { return aide_with_storage<bf16_store_t>(dx_bf16, [&](auto dt) {
+        return aide_with_storage<bf16_store_t>(x_bf16, [&](auto xt) {
+            return maxpool_bwd_t(xt.cast(x), x_bs, gt.cast(dy), dy_bs, dt.cast(dx), dx_bs, N, C, H, W, accumulate, stream);
+        });
+    }); });
 }
 
 // workgroups of the tiled up-sampling backward per tile position: each walks planes g, g + groups, ... -- about UB_WGS
@@ -677,10 +675,9 @@ int aide_upsample2x_bilinear_fwd(const float* x, int64_t x_bs, float* y, int64_t
 int aide_upsample2x_bilinear_fwd_mixed(const void* x, int x_bf16, int64_t x_bs, void* y, int y_bf16, int64_t y_bs, int N,
                                        int C, int H, int W, hipStream_t stream) {
     if ((2 * W) % 4 || y_bs % 4) return AIDE_ERR_ARG;
-    if (x_bf16) return y_bf16 ? upsample_fwd_t((const bf16_store_t*)x, x_bs, (bf16_store_t*)y, y_bs, N, C, H, W, stream)
-                              : upsample_fwd_t((const bf16_store_t*)x, x_bs, (float*)y, y_bs, N, C, H, W, stream);
-    return y_bf16 ? upsample_fwd_t((const float*)x, x_bs, (bf16_store_t*)y, y_bs, N, C, H, W, stream)
-                  : upsample_fwd_t((const float*)x, x_bs, (float*)y, y_bs, N, C, H, W, stream);
+    return aide_with_storage<bf16_store_t>(x_bf16, [&](auto xt) { return aide_with_storage<bf16_store_t>(y_bf16, [&](auto yt) {
+        return upsample_fwd_t(xt.cast(x), x_bs, yt.cast(y), y_bs, N, C, H, W, stream);
+    }); });
 }
 
 int aide_upsample2x_bilinear_bwd(const float* dy, int64_t dy_bs, float* dx, int64_t dx_bs, int N, int C,
@@ -713,16 +710,16 @@ int aide_upsample2x_bilinear_bwd_mixed(const void* dy, int dy_bf16, int64_t dy_b
     const int pstep = ub_plane_groups(tw * th, N * C);
     const dim3 grid((unsigned)((long)tw * th * pstep));
     const double kt_bytes = (double)N * C * H * W * (4.0 * (dy_bf16 ? 2 : 4) + (accumulate ? 2.0 : 1.0) * (dx_bf16 ? 2 : 4));
-#define AIDE_UB(GT, DT)                                                                                                          \
-    do {                                                                                                                         \
-        if (fast) AIDE_LAUNCH_TIMED(AIDE_KT_UPSAMPLE, kt_bytes, (upsample2x_bwd_tiled_kernel<GT, DT, true>), grid, dim3(256), 0, stream, \
-                                    (const GT*)dy, (long)dy_bs, (DT*)dx, (long)dx_bs, C, H, W, tw, tw * th, N * C, pstep, accumulate); \
-        else AIDE_LAUNCH_TIMED(AIDE_KT_UPSAMPLE, kt_bytes, (upsample2x_bwd_tiled_kernel<GT, DT, false>), grid, dim3(256), 0, stream, \
-                               (const GT*)dy, (long)dy_bs, (DT*)dx, (long)dx_bs, C, H, W, tw, tw * th, N * C, pstep, accumulate); \
-    } while (0)
-    if (dy_bf16) { if (dx_bf16) AIDE_UB(bf16_store_t, bf16_store_t); else AIDE_UB(bf16_store_t, float); }
-    else { if (dx_bf16) AIDE_UB(float, bf16_store_t); else AIDE_UB(float, float); }
-#undef AIDE_UB
+    aide_with_storage<bf16_store_t>(dy_bf16, [&](auto gt) { aide_with_storage<bf16_store_t>(dx_bf16, [&](auto dt) {
+        using GT = typename decltype(gt)::type;
+        using DT = typename decltype(dt)::type;
+        if (fast)
+            AIDE_LAUNCH_TIMED(AIDE_KT_UPSAMPLE, kt_bytes, (upsample2x_bwd_tiled_kernel<GT, DT, true>), grid, dim3(256), 0, stream,
+                              gt.cast(dy), (long)dy_bs, dt.cast(dx), (long)dx_bs, C, H, W, tw, tw * th, N * C, pstep, accumulate);
+        else
+            AIDE_LAUNCH_TIMED(AIDE_KT_UPSAMPLE, kt_bytes, (upsample2x_bwd_tiled_kernel<GT, DT, false>), grid, dim3(256), 0, stream,
+                              gt.cast(dy), (long)dy_bs, dt.cast(dx), (long)dx_bs, C, H, W, tw, tw * th, N * C, pstep, accumulate);
+    }); });
     return aide_launch_status();
 }
 

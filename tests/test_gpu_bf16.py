@@ -114,7 +114,8 @@ def test_bf16_storage_variants(dev):
                 assert torch.equal(dw_a, dw_b), 'bf16 dz wgrad'
 
 
-@pytest.mark.parametrize('shape', [(2, 32, 32, 32), (4, 64, 16, 16), (1, 8, 6, 5)])
+@pytest.mark.parametrize('shape', [(2, 32, 32, 32), (4, 64, 16, 16), (1, 8, 6, 5),
+                                   (8, 1, 514, 514)])        # (two passes, 4 wide, whatever the storage)
 def test_bn_on_bf16_storage(dev, shape):
     """BatchNorm forward / backward on a bf16-stored z and into a bf16-stored dz: bit-identical to the fp32-storage
     kernels on the widened z, with dz narrowed RNE."""

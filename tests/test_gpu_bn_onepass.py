@@ -40,7 +40,11 @@ SHAPES = [
     (5, 8, 20, 20),         # 500 units, C * S small -> Q 1, S 2
     (1, 16, 48, 32),
     (2, 3, 16, 16),
-    (8, 16, 512, 256),      # 262144 units: Q 8, S 128 (the largest one-pass channel)
+    (8, 16, 512, 256),      # 131072 units of 8: Q 4, S 128
+    (16, 2, 512, 512),      # 524288 units of 8: Q 8, S 256 (more than 256 * 256 * 4 units per channel)
+    (4, 2, 258, 258),       # planes of 4 * odd values -> units of 4 on a large channel: Q 2, S 131
+    (8, 2, 258, 258),       # ... Q 4
+    (16, 2, 258, 258),      # ... Q 8
 ]
 
 
@@ -129,7 +133,9 @@ def test_onepass_repeatable_beside_a_full_chip(dev):
 
 
 @pytest.mark.parametrize('case', [(4, 4, 128, 64, 64, 0), (2, 4, 256, 32, 32, 0), (4, 4, 32, 128, 128, 0), (3, 2, 512, 16, 16, 0),
-                                  (4, 4, 128, 64, 64, 2), (4, 4, 512, 32, 32, 4), (2, 3, 256, 32, 32, 3)])
+                                  (4, 4, 128, 64, 64, 2), (4, 4, 512, 32, 32, 4), (2, 3, 256, 32, 32, 3),
+                                  # units of 8 / 4 at 8 / 2 / 4 / 8 units per thread (Q of coop_plan)
+                                  (9, 2, 2, 512, 512, 0), (4, 2, 2, 258, 258, 0), (8, 2, 2, 258, 258, 2), (16, 2, 2, 258, 258, 2)])
 def test_onepass_groups_equal_sequential_forwards(dev, case):
     """a stacked batch (groups walked inside the kernel) against one launch per group: activations, running statistics, the
     saved coefficients -- bit for bit; z as it is (splitk = 0) or summed from split-K slabs"""
@@ -191,7 +197,9 @@ def test_onepass_groups_equal_sequential_forwards(dev, case):
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize('case', [(4, 128, 64, 64, 2), (4, 512, 32, 32, 4), (4, 1024, 16, 16, 16), (4, 64, 128, 128, 3)])
+@pytest.mark.parametrize('case', [(4, 128, 64, 64, 2), (4, 512, 32, 32, 4), (4, 1024, 16, 16, 16), (4, 64, 128, 128, 3),
+                                  # Q 8 on units of 8; Q 2 / 4 / 8 on units of 4; a channel beyond the one-pass form (two passes, 4 wide)
+                                  (9, 2, 512, 512, 2), (4, 2, 258, 258, 2), (8, 2, 258, 258, 3), (16, 2, 258, 258, 2), (8, 2, 514, 514, 2)])
 def test_onepass_fwd_from_splitk_slabs(dev, case):
     """forward fed by split-K slabs == slab reduce (split order, + bias) followed by the plain forward, bit for bit"""
     import ctypes
@@ -253,7 +261,8 @@ def test_onepass_bf16_storage(dev, shape):
     assert torch.equal(a32.bfloat16(), a16) and torch.equal(dz32.bfloat16(), dz16)
 
 
-@pytest.mark.parametrize('shape', [(4, 64, 256, 256), (4, 128, 64, 64), (2, 512, 32, 32), (3, 24, 40, 48), (1, 8, 64, 32)])
+@pytest.mark.parametrize('shape', [(4, 64, 256, 256), (4, 128, 64, 64), (2, 512, 32, 32), (3, 24, 40, 48), (1, 8, 64, 32),
+                                   (9, 2, 512, 512)])        # (Q 8)
 def test_onepass_bwd_with_pooled_gradient(dev, shape):
     """aide_bn_relu_bwd_pool: dA + the gradient of MaxPool2d(2, 2)(relu(bn(z))) routed to the window arg-max inside the BatchNorm
     backward == aide_maxpool2x2_bwd(accumulate) into dA followed by the plain backward, bit for bit -- on activations with many
@@ -296,7 +305,9 @@ def test_onepass_bwd_with_pooled_gradient(dev, shape):
         _close(out[0], zr.grad, rtol=1e-4, what='dz vs autograd')
 
 
-@pytest.mark.parametrize('case', [(4, 64, 256, 256, 2), (2, 64, 64, 48, 3), (3, 32, 20, 20, 8), (1, 16, 32, 32, 1)])
+@pytest.mark.parametrize('case', [(4, 64, 256, 256, 2), (2, 64, 64, 48, 3), (3, 32, 20, 20, 8), (1, 16, 32, 32, 1),
+                                  # units of 8 at Q 2 / 8, units of 4 at Q 2 / 4 / 8
+                                  (4, 128, 64, 64, 4), (9, 2, 512, 512, 2), (4, 2, 258, 258, 5), (8, 2, 258, 258, 6), (16, 2, 258, 258, 7)])
 def test_onepass_bwd_with_head_gradient(dev, case):
     """aide_bn_relu_bwd_head: the 1x1 head's data gradient sum_k w[k][c] dlogits[k] formed inside the BatchNorm backward of the layer
     under the head == aide_head1x1_bwd's dx followed by the plain backward, bit for bit (2 .. 8 classes; last_conv1, fuseunet.py:41)."""
@@ -364,7 +375,8 @@ def test_onepass_two_kernels_at_once(dev):
                 assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize('case', [(4, 1, 32, 256, 256), (4, 4, 64, 128, 128), (2, 3, 24, 40, 48), (4, 1, 128, 64, 64)])
+@pytest.mark.parametrize('case', [(4, 1, 32, 256, 256), (4, 4, 64, 128, 128), (2, 3, 24, 40, 48), (4, 1, 128, 64, 64),
+                                  (9, 1, 2, 512, 512)])     # (Q 8)
 def test_onepass_fwd_with_pooled_output(dev, case):
     """aide_bn_train_fwd_pool: the activation AND max_pool2d(activation, 2) from one launch == the plain forward (per group, in order)
     followed by aide_maxpool2x2_fwd, bit for bit -- activations, pooled tensor, running statistics, saved coefficients."""

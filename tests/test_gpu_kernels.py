@@ -87,7 +87,8 @@ def test_conv3x3_channel_slices(dev):
     assert (big_out[:, :64] == 7.0).all() and (big_out[:, 128:] == 7.0).all()
 
 
-@pytest.mark.parametrize('shape', [(4, 32, 64, 64), (2, 64, 16, 16), (3, 8, 20, 20)])
+@pytest.mark.parametrize('shape', [(4, 32, 64, 64), (2, 64, 16, 16), (3, 8, 20, 20),
+                                   (8, 2, 514, 514)])        # a channel beyond the one-pass form, planes of 4 * odd values: two passes, 4 wide
 def test_bn_relu_fwd_bwd(dev, shape):
     from aide_amd import ops
     n, c, h, w = shape
@@ -187,7 +188,9 @@ def test_bn_relu_bwd_completion_event(dev, shape):
         assert torch.equal(o, ref)
 
 
-@pytest.mark.parametrize('case', [(4, 512, 16, 16, 8), (4, 256, 32, 32, 4), (2, 128, 64, 64, 2)])
+@pytest.mark.parametrize('case', [(4, 512, 16, 16, 8), (4, 256, 32, 32, 4), (2, 128, 64, 64, 2),
+                                  # 2 / 4 units of 8 per thread, 2 units of 4 (Q of coop_plan)
+                                  (4, 128, 64, 64, 2), (4, 256, 64, 64, 2), (6, 512, 16, 16, 4)])
 def test_bn_relu_bwd_from_splitk_slabs(dev, case):
     """BatchNorm backward that reads its dA from the split-K slabs of the data-gradient convolution (the engine's
     conv2 -> conv1 pairs at the 64x64 .. 16x16 levels): bit-identical to the split reduce followed by bn_relu_bwd, and the
