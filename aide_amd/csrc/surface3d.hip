@@ -1,0 +1,291 @@
+// Spacing-aware surface distances of a predicted volume P against its target T on the device: the raw sums behind RAVD, ASSD
+// and MSSD (include/aide_hip.h "per-case evaluation"; the definitions are DESIGN.md section 4 "Surface distances").
+//
+// Foreground of an operand X: X != 0 (cls < 0) or X == cls.  Border: foreground with a face neighbour that is not foreground
+// or lies outside the volume.  D_X(v) = the exact Euclidean distance, in fp64 and in units of the voxel spacing, from v to the
+// nearest border voxel of X.  Launches (operand = blockIdx.y wherever both are handled):
+//   1 surf_border   one thread per voxel of the two strided operands: the border maps as bytes in logical raster order,
+//                   n_P, n_T, V_P, V_T with integer atomics (one per wave and counter).  From here on no stride is read.
+//   2 surf_scan2    one thread per line along d2: g = integer distance to the nearest border voxel of the line, NONE when the
+//                   line holds none (forward sweep, backward sweep)
+//   3 surf_minplus<false>  along d1: f(i1) = min over j1 of (sp1 * (i1 - j1))^2 + (sp2 * g(j1))^2, +inf where g is NONE.
+//                   A workgroup owns 64 neighbouring lines and walks them in chunks: 32 candidates in LDS, 32 results in
+//                   registers (8 per thread); brute force, branch-free.
+//   4 surf_minplus<true>   the same walk along d0 on the OTHER operand's f, kept only at the border voxels of this operand:
+//                   sqrt, the optional distance map, and per workgroup one fp64 sum and one max, reduced in a fixed order and
+//                   written to the workgroup's own slot
+//   5 surf_finish   one workgroup adds the slots in slot order and writes S_PT, S_TP, M_PT, M_TP
+// No workgroup waits for another, no floating-point atomic exists, every word of the workspace that is read was written by
+// an earlier launch of the same call, and the order of every floating-point sum is fixed by the launch geometry: two calls on
+// the same inputs give the same bytes.  "No border voxel" is the integer NONE after launch 2 and +inf after launch 3
+// (inf + x = inf, min keeps the finite side, no product has an infinite factor: the spacings are finite); launch 4 takes a
+// square root only of a finite minimum, which exists for every voxel as soon as the other operand has one border voxel.
+// All indices come from integers.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int NONE = 0x7fffffff;   // surf_scan2: the line holds no border voxel (distances are < 2^31 - 1)
+constexpr int COLS = 64;           // lines per workgroup = lanes of a wave: LDS rows are read without a bank conflict
+constexpr int ROWS = 4;            // waves per workgroup, each owns R results of a chunk
+constexpr int R = 8;
+constexpr int OC = ROWS * R;       // results per chunk
+constexpr int CH = 32;             // candidates per chunk in LDS: CH * COLS doubles = 16 KiB
+
+struct Operand {
+    const void* p;
+    long s0, s1, s2;
+    int u8;
+};
+
+__device__ __forceinline__ bool fg_at(const Operand& X, long off, int cls) {
+    const long long v = X.u8 ? (long long)static_cast<const unsigned char*>(X.p)[off] : static_cast<const long long*>(X.p)[off];
+    return cls < 0 ? v != 0 : v == (long long)cls;
+}
+
+// -> 0: background, 1: inner foreground, 2: border
+__device__ __forceinline__ int classify(const Operand& X, int i0, int i1, int i2, int d0, int d1, int d2, int cls) {
+    const long off = (long)i0 * X.s0 + (long)i1 * X.s1 + (long)i2 * X.s2;
+    if (!fg_at(X, off, cls)) return 0;
+    bool inner = i0 > 0 && i0 + 1 < d0 && i1 > 0 && i1 + 1 < d1 && i2 > 0 && i2 + 1 < d2;
+    if (inner)
+        inner = fg_at(X, off - X.s0, cls) && fg_at(X, off + X.s0, cls) && fg_at(X, off - X.s1, cls) &&
+                fg_at(X, off + X.s1, cls) && fg_at(X, off - X.s2, cls) && fg_at(X, off + X.s2, cls);
+    return inner ? 1 : 2;
+}
+
+// cnt[0..3] += n_P, n_T, V_P, V_T (zeroed by the launcher); bmap[2][n]
+__global__ __launch_bounds__(256) void surf_border_kernel(Operand P, Operand T, int d0, int d1, int d2, int n, int cls,
+                                                          unsigned char* __restrict__ bmap,
+                                                          unsigned long long* __restrict__ cnt) {
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    int kp = 0, kt = 0;
+    if (u < (unsigned)n) {
+        const int i = (int)u, plane = d1 * d2, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
+        kp = classify(P, i0, i1, i2, d0, d1, d2, cls);
+        kt = classify(T, i0, i1, i2, d0, d1, d2, cls);
+        bmap[i] = kp == 2;
+        bmap[(size_t)n + i] = kt == 2;
+    }
+    const unsigned long long bp = __ballot(kp == 2), bt = __ballot(kt == 2), vp = __ballot(kp != 0), vt = __ballot(kt != 0);
+    const int lane = threadIdx.x & 63;
+    const unsigned long long mine = lane == 0 ? bp : lane == 1 ? bt : lane == 2 ? vp : vt;
+    if (lane < 4 && mine) atomicAdd(cnt + lane, (unsigned long long)__popcll(mine));
+}
+
+// g[2][n]: one thread per line (i0, i1) of an operand
+__global__ __launch_bounds__(256) void surf_scan2_kernel(const unsigned char* __restrict__ bmap, int lines, int d2, int n,
+                                                         int* __restrict__ g) {
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (unsigned)lines) return;
+    const size_t base = (size_t)blockIdx.y * n + (size_t)u * d2;
+    const unsigned char* b = bmap + base;
+    int* o = g + base;
+    int last = -1;
+    for (int i = 0; i < d2; ++i) {
+        if (b[i]) last = i;
+        o[i] = last >= 0 ? i - last : NONE;
+    }
+    int next = -1;
+    for (int i = d2 - 1; i >= 0; --i) {
+        if (b[i]) next = i;
+        if (next >= 0) o[i] = min(o[i], next - i);
+    }
+}
+
+// Lines of length L and element stride `stride`; line c of ncol starts at (c / inner) * outer + c % inner.
+//   along d1: L = d1, stride = d2, inner = d2, outer = d1 * d2, ncol = d0 * d2
+//   along d0: L = d0, stride = d1 * d2, inner = ncol = d1 * d2 (outer unused)
+struct Lines {
+    int L, stride, inner, outer, ncol, n;
+    double sp;       // spacing along the line
+    double sp_in;    // !LAST: spacing of the scanned dim (d2)
+};
+
+// !LAST: f[op] from g[op].  LAST (blockIdx.y = op: 0 measures the border voxels of P against T, 1 the reverse):
+// dist[op][i] = sqrt(min) at the border voxels of operand op against f[1 - op], -1 elsewhere; part[op][blockIdx.x] = {sum, max}
+template <bool LAST>
+__global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* __restrict__ g, double* __restrict__ f,
+                                                           const unsigned char* __restrict__ bmap,
+                                                           double* __restrict__ dist, double* __restrict__ part) {
+    __shared__ double h[CH][COLS];
+    __shared__ double red[2][256];
+    const int op = blockIdx.y, col = threadIdx.x & 63, row = threadIdx.x >> 6;
+    const long c = (long)blockIdx.x * COLS + col;
+    const bool live = c < q.ncol;
+    const int cc = live ? (int)c : 0;
+    const size_t start = (size_t)(cc / q.inner) * q.outer + cc % q.inner;
+    const size_t src = (size_t)(LAST ? 1 - op : op) * q.n + start, dst = (size_t)op * q.n + start;
+    const double inf = __builtin_inf();
+    double sum = 0.0, mx = 0.0;
+    for (int o0 = 0; o0 < q.L; o0 += OC) {
+        const int first = o0 + row * R;          // this thread's results: first .. first + R - 1
+        double best[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) best[r] = inf;
+        for (int j0 = 0; j0 < q.L; j0 += CH) {
+            __syncthreads();                     // the previous chunk is read to the end
+#pragma unroll
+            for (int k = 0; k < CH / ROWS; ++k) {
+                const int jl = k * ROWS + row, j = j0 + jl;
+                double v = inf;
+                if (live && j < q.L) {
+                    if (LAST) v = f[src + (size_t)j * q.stride];
+                    else {
+                        const int gi = g[src + (size_t)j * q.stride];
+                        if (gi != NONE) { const double t = q.sp_in * (double)gi; v = t * t; }
+                    }
+                }
+                h[jl][col] = v;
+            }
+            __syncthreads();
+            double dd = (double)(first - j0);    // result index - candidate index, exact
+#pragma unroll 4
+            for (int jl = 0; jl < CH; ++jl) {
+                const double hv = h[jl][col];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double t = q.sp * (dd + (double)r);
+                    best[r] = fmin(best[r], t * t + hv);
+                }
+                dd -= 1.0;
+            }
+        }
+        if (LAST) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = first + r;
+                if (!live || i >= q.L) continue;
+                const size_t at = dst + (size_t)i * q.stride;
+                double d = -1.0;
+                if (bmap[at] && best[r] < inf) {
+                    d = sqrt(best[r]);
+                    sum += d;
+                    mx = fmax(mx, d);
+                }
+                if (dist) dist[at] = d;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = first + r;
+                if (live && i < q.L) f[dst + (size_t)i * q.stride] = best[r];
+            }
+        }
+    }
+    if (LAST) {
+        red[0][threadIdx.x] = sum;
+        red[1][threadIdx.x] = mx;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) {
+                red[0][threadIdx.x] += red[0][threadIdx.x + s];
+                red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            double* slot = part + 2 * ((size_t)op * gridDim.x + blockIdx.x);
+            slot[0] = red[0][0];
+            slot[1] = red[1][0];
+        }
+    }
+}
+
+// out[4], out[5] = S_PT, S_TP; out[6], out[7] = M_PT, M_TP from part[2][slots][2]: thread t adds the slots t, t + 256, ... in
+// rising order, then the 256 partial sums fold pairwise
+__global__ __launch_bounds__(256) void surf_finish_kernel(const double* __restrict__ part, int slots, double* __restrict__ out) {
+    __shared__ double red[2][256];
+    for (int op = 0; op < 2; ++op) {
+        double sum = 0.0, mx = 0.0;
+        for (int s = threadIdx.x; s < slots; s += 256) {
+            const double* slot = part + 2 * ((size_t)op * slots + s);
+            sum += slot[0];
+            mx = fmax(mx, slot[1]);
+        }
+        __syncthreads();
+        red[0][threadIdx.x] = sum;
+        red[1][threadIdx.x] = mx;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) {
+                red[0][threadIdx.x] += red[0][threadIdx.x + s];
+                red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            out[4 + op] = red[0][0];
+            out[6 + op] = red[1][0];
+        }
+    }
+}
+
+bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
+    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
+    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
+    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
+}
+
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+// f [2][n] fp64 | g [2][n] int32 | bmap [2][n] bytes | slots [2][ceil(n / 64)][2] fp64 (d1 * d2 <= n: as many as any shape needs)
+size_t aide_surface3d_ws_bytes(int64_t nvox) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    const size_t n = (size_t)nvox;
+    const size_t slots = (n + COLS - 1) / COLS;
+    return align16(2 * n * sizeof(double)) + align16(2 * n * sizeof(int)) + align16(2 * n) + 4 * slots * sizeof(double) + 16;
+}
+
+int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                          int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1,
+                          double sp2, int cls, void* out, double* dist, void* ws, hipStream_t stream) {
+    if (!dims_ok(d0, d1, d2) || !p || !t || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    if ((p_u8 != 0 && p_u8 != 1) || (t_u8 != 0 && t_u8 != 1)) return AIDE_ERR_ARG;
+    if (!(sp0 > 0.0 && sp1 > 0.0 && sp2 > 0.0) || !std::isfinite(sp0) || !std::isfinite(sp1) || !std::isfinite(sp2))
+        return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    const int plane = (int)(d1 * d2);
+    const long cols1 = (long)d0 * d2, cols0 = plane;                        // lines along d1, along d0
+    const long slots = (cols0 + COLS - 1) / COLS;
+    hipError_t e = hipMemsetAsync(out, 0, 8 * sizeof(double), stream);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return 0;
+    char* w = static_cast<char*>(ws);
+    double* f = reinterpret_cast<double*>(w);
+    w += align16(2 * (size_t)n * sizeof(double));
+    int* g = reinterpret_cast<int*>(w);
+    w += align16(2 * (size_t)n * sizeof(int));
+    unsigned char* bmap = reinterpret_cast<unsigned char*>(w);
+    w += align16(2 * (size_t)n);
+    double* part = reinterpret_cast<double*>(w);
+    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2, p_u8}, T{t, (long)t_s0, (long)t_s1, (long)t_s2, t_u8};
+    const unsigned nb = (unsigned)(((long)n + 255) / 256);
+    const int lines = (int)(d0 * d1);
+    Lines a1, a0;
+    a1.L = (int)d1; a1.stride = (int)d2; a1.inner = (int)d2; a1.outer = plane; a1.ncol = (int)cols1; a1.n = n;
+    a1.sp = sp1; a1.sp_in = sp2;
+    a0.L = (int)d0; a0.stride = plane; a0.inner = plane; a0.outer = 0; a0.ncol = (int)cols0; a0.n = n;
+    a0.sp = sp0; a0.sp_in = 0.0;
+    const dim3 block(256);
+    const double bytes_in = (double)n * ((p_u8 ? 1 : 8) + (t_u8 ? 1 : 8));
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes_in + 2.0 * n, surf_border_kernel, dim3(nb), block, 0, stream, P, T, (int)d0, (int)d1,
+                      (int)d2, n, cls, bmap, static_cast<unsigned long long*>(out));
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 10.0 * n, surf_scan2_kernel, dim3((unsigned)((lines + 255) / 256), 2), block, 0, stream,
+                      (const unsigned char*)bmap, lines, (int)d2, n, g);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 24.0 * n, surf_minplus_kernel<false>, dim3((unsigned)((cols1 + COLS - 1) / COLS), 2), block,
+                      0, stream, a1, (const int*)g, f, (const unsigned char*)bmap, (double*)nullptr, (double*)nullptr);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (dist ? 34.0 : 18.0) * n, surf_minplus_kernel<true>, dim3((unsigned)slots, 2), block, 0,
+                      stream, a0, (const int*)g, f, (const unsigned char*)bmap, dist, part);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, surf_finish_kernel, dim3(1), block, 0, stream, (const double*)part, (int)slots,
+                      static_cast<double*>(out));
+    return aide_launch_status();
+}
+
+}  // extern "C"

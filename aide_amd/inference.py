@@ -224,7 +224,7 @@ def _case_scores_classes(pred, target, c):
     return dict(Dice=dice, IoU=iou, TP=tp.copy(), TN=n - si - st + tp, FP=si - tp, FN=st - tp)
 
 
-def case_scores(pred, target, num_classes=None):
+def case_scores(pred, target, num_classes=None, spacing=None):
     """Per-case scores of the evaluation script (evalchaos_comparison_1cases.py:116-141, 238-242) for a predicted label
     volume against its target: dict(Dice, IoU, TP, TN, FP, FN).  HIP tensors: one confusion launch and one copy of four
     int64 sums to the host; anything else: the same sums in int64 on the CPU.  TP = sum p*t, FP = sum p - TP,
@@ -232,7 +232,16 @@ def case_scores(pred, target, num_classes=None):
     (sum p + sum t) and IoU = TP / (sum p + sum t - TP) as float64 true division like numpy's (0/0 -> nan, x/0 -> inf).
     num_classes=C (2 .. 8): the same six scores per class for multi-class label volumes, as arrays of [C] (Dice, IoU float64,
     the rest int64) with p_c = (pred == c), t_c = (target == c); a label outside [0, C) belongs to no class.  HIP tensors: one
-    launch of aide_mc_counts_labels and one copy of C * 3 int64."""
+    launch of aide_mc_counts_labels and one copy of C * 3 int64.
+    spacing=(sp0, sp1, sp2), the edge lengths of a voxel along the three dims of the volumes (the evaluation script's
+    `voxelspacing`, :181, 192-194): the dict also carries RAVD, ASSD and MSSD of `utils.metrics3d.surface_scores`; without it
+    the dict is the six scores above and nothing else."""
+    if spacing is not None:
+        from .utils.metrics3d import surface_scores
+        res = case_scores(pred, target, num_classes)
+        surf = surface_scores(pred, target, spacing, num_classes)
+        res.update((k, surf[k]) for k in ('RAVD', 'ASSD', 'MSSD'))
+        return res
     if num_classes is not None:
         return _case_scores_classes(pred, target, int(num_classes))
     dev = [x for x in (pred, target) if isinstance(x, torch.Tensor) and x.is_cuda]

@@ -562,6 +562,27 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
                         int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
                         aide_stream_t stream);
 
+/* ---- surface distances in millimetres: the raw sums behind RAVD, ASSD and MSSD, the CHAOS challenge's other three scores.
+ * The reference reads every case's PixelSpacing and SliceThickness into `voxelspacing`
+ * (evalchaos_comparison_1cases.py:181, 192-194) and never uses them; its utils/metrics3d.py is four import lines.
+ * Operands as in aide_case_confusion; (sp0, sp1, sp2) = edge lengths of a voxel along the logical dims.  Foreground of an
+ * operand X: X != 0 (cls < 0) or X == cls.  Border: foreground with at least one of the six face neighbours not foreground or
+ * outside the volume.  D_X(v) = min over u in border(X) of sqrt(sum_k (sp_k * (v_k - u_k))^2) in fp64: exact, no chamfer. */
+/* workspace of aide_surface3d_scores for nvox = d0 * d1 * d2 voxels (16-byte aligned); 0 for nvox >= 2^31 */
+size_t aide_surface3d_ws_bytes(int64_t nvox);
+/* out = 8 words of 8 bytes: int64 n_P, n_T (border voxels), V_P, V_T (foreground voxels); double S_PT = sum over border(P)
+ * of D_T, S_TP, M_PT = max of the same values, M_TP (sums and maxima 0 where an operand has no border: the caller decides
+ * from n_P and n_T).  dist: NULL, or [2][d0 * d1 * d2] in logical raster order: dist[0] = D_T at the border voxels of P,
+ * dist[1] = D_P at those of T, -1.0 everywhere else (everywhere when the other operand has no border).  Five launches, no
+ * floating-point atomic: two calls on the same inputs give the same bytes, whatever the workspace held.  AIDE_ERR_ARG before
+ * any launch for a null p / t / out / ws, a misaligned ws, d0 * d1 * d2 >= 2^31, a spacing that is not
+ * positive and finite; an empty volume only clears out.  (sp_k * d_k)^2 must stay finite in fp64: a candidate whose squared
+ * distance overflows counts as no candidate. */
+int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2,
+                          const void* t, int t_u8, int64_t t_s0, int64_t t_s1, int64_t t_s2,
+                          int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1, double sp2,
+                          int cls, void* out, double* dist, void* ws, aide_stream_t stream);
+
 /* ---- the same for all cases of an epoch at once: K ragged cases concatenated as [S_total][H][W] (contiguous; what the
  * label map yields when fed all slices) with a DEVICE table slice_start[K + 1] (int64, non-decreasing, slice_start[0] >= 0,
  * slice_start[K] <= S_total; an entry outside that is clamped so that no access leaves the buffers).  Case k's logical
