@@ -23,6 +23,11 @@
 // order is its own raster order: the same invariants, the same tie rule, and a union never leaves the range because a tile
 // never leaves its case.  Every launch has the grid (chunks of the plane, K): blockIdx.y is the case, the block walks the
 // case's slices, and the number of launches is the per-case form's five whatever K is.
+//
+// Per-class form (aide_keep_largest_cc3d_classes[_batched]): blobs of different values are separate sets already, so launches
+// 1 - 3 are shared as they are and only select and write differ: one key per class value 1 .. C - 1 (the value read at the
+// root), out[i] = the voxel's own class where its root is that class's winner.  The 3 C control words per volume (keys, root
+// counts, area sums) are cleared by one memset in front of launch 1: five launches and one memset whatever C and K are.
 #include "common.h"
 
 namespace {
@@ -262,6 +267,125 @@ __global__ __launch_bounds__(256) void lcc_write_kernel(const int* __restrict__ 
     const int best = ctrl[1] ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
     const int p = parent[i];
     out[i] = (best >= 0 && p >= 0 && find_plain(parent, p) == best) ? 1 : 0;
+}
+
+// ---- per-class form of select and write: one winner per class value 1 .. C - 1 (C <= MAXC) ----
+// Control words of a volume (case k of K; K = 1, k = 0 for the single volume), all cleared by one memset before launch 1:
+// ctrl[k * C + c] = max key over the roots of class c, ctrl[(K + k) * C + c] = number of roots (components) of class c,
+// ctrl[(2 K + k) * C + c] = sum of their areas (voxels of class c).  Word c = 0 of every group stays zero.
+constexpr int MAXC = 8;
+
+// 1 .. C - 1, or 0 for a value that belongs to no class (0, negative, >= C)
+__device__ __forceinline__ int class_of(long long v, int C) { return (v > 0 && v < C) ? (int)v : 0; }
+
+struct ClassAcc {                                 // a thread's running key, root count and area sum per class: registers
+    unsigned long long key[MAXC - 1];
+    unsigned cnt[MAXC - 1], vox[MAXC - 1];        // a sum of areas of distinct roots never exceeds the voxel count < 2^31
+};
+
+template <bool STATS>
+__device__ __forceinline__ void class_add(ClassAcc& a, int c, int i, int ar) {
+    const unsigned long long key = ((unsigned long long)(unsigned)ar << 32) | (unsigned)(0x7fffffff - i);
+#pragma unroll
+    for (int j = 0; j < MAXC - 1; ++j)
+        if (c == j + 1) {
+            a.key[j] = umax64(a.key[j], key);
+            if (STATS) { a.cnt[j] += 1u; a.vox[j] += (unsigned)ar; }
+        }
+}
+
+// wave reduce with __shfl_xor, block reduce through LDS, then thread j commits class j + 1: at most one atomicMax (and, with
+// STATS, two integer atomicAdd) per (block, class), none where the block saw no root of the class
+template <bool STATS>
+__device__ __forceinline__ void class_commit(ClassAcc& a, int C, unsigned long long* __restrict__ keys,
+                                             unsigned long long* __restrict__ cnts, unsigned long long* __restrict__ voxs) {
+    __shared__ unsigned long long sk[4][MAXC - 1];
+    __shared__ unsigned sc[4][MAXC - 1], sv[4][MAXC - 1];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < MAXC - 1; ++j) {
+        if (j >= C - 1) break;                    // uniform
+        unsigned long long key = a.key[j];
+        unsigned cn = a.cnt[j], vx = a.vox[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            key = umax64(key, __shfl_xor(key, o));
+            if (STATS) { cn += __shfl_xor(cn, o); vx += __shfl_xor(vx, o); }
+        }
+        if (lane == 0) {
+            sk[wid][j] = key;
+            if (STATS) { sc[wid][j] = cn; sv[wid][j] = vx; }
+        }
+    }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j < C - 1) {
+        const unsigned long long key = umax64(umax64(sk[0][j], sk[1][j]), umax64(sk[2][j], sk[3][j]));
+        if (key) atomicMax(keys + j + 1, key);
+        if (STATS) {
+            const unsigned cn = sc[0][j] + sc[1][j] + sc[2][j] + sc[3][j], vx = sv[0][j] + sv[1][j] + sv[2][j] + sv[3][j];
+            if (cn) atomicAdd(cnts + j + 1, (unsigned long long)cn);
+            if (vx) atomicAdd(voxs + j + 1, (unsigned long long)vx);
+        }
+    }
+}
+
+// best[c] = the chosen root of class c, -1 where the class has no root (key 0) and for c = 0; then a block barrier
+__device__ __forceinline__ void class_best(const unsigned long long* __restrict__ keys, int C, int* best) {
+    const int c = threadIdx.x;
+    if (c < MAXC) {
+        const unsigned long long key = (c >= 1 && c < C) ? keys[c] : 0ull;
+        best[c] = key ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
+    }
+    __syncthreads();
+}
+
+// stats[c][0..2] = components, voxels, voxels of the kept component of class c; row 0 zeros (threads 0 .. C - 1 of one block)
+__device__ __forceinline__ void class_stats(const unsigned long long* __restrict__ keys,
+                                            const unsigned long long* __restrict__ cnts,
+                                            const unsigned long long* __restrict__ voxs, int C, long long* __restrict__ stats) {
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    stats[3 * c] = c ? (long long)cnts[c] : 0;
+    stats[3 * c + 1] = c ? (long long)voxs[c] : 0;
+    stats[3 * c + 2] = c ? (long long)(keys[c] >> 32) : 0;
+}
+
+// the value is read at the roots only, as in lcc_select_kernel
+template <bool STATS>
+__global__ __launch_bounds__(256) void lcc_select_classes_kernel(Vol g, const int* __restrict__ parent,
+                                                                 const int* __restrict__ area, int n, int C,
+                                                                 unsigned long long* __restrict__ ctrl) {
+    ClassAcc a = {};
+    const int plane = g.d1 * g.d2;
+    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
+        const int i = (int)u;
+        if (parent[i] != i) continue;
+        const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
+        const int c = class_of(g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2], C);
+        if (c) class_add<STATS>(a, c, i, area[i]);
+    }
+    class_commit<STATS>(a, C, ctrl, ctrl + C, ctrl + 2 * C);
+}
+
+// out[i] = the voxel's own value v where v is a class and find(i) is the chosen root of that class, 0 elsewhere
+__global__ __launch_bounds__(256) void lcc_write_classes_kernel(Vol g, const int* __restrict__ parent, int n, int C,
+                                                                const unsigned long long* __restrict__ ctrl,
+                                                                unsigned char* __restrict__ out, long long* __restrict__ stats) {
+    __shared__ int best[MAXC];
+    class_best(ctrl, C, best);
+    if (stats && blockIdx.x == 0) class_stats(ctrl, ctrl + C, ctrl + 2 * C, C, stats);
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (unsigned)n) return;
+    const int i = (int)u, p = parent[i];
+    int o = 0;
+    if (p >= 0) {
+        const int plane = g.d1 * g.d2;
+        const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
+        const int c = class_of(g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2], C);
+        if (c && best[c] >= 0 && find_plain(parent, p) == best[c]) o = c;
+    }
+    out[i] = (unsigned char)o;
 }
 
 // ---- confusion sums: out[0..3] = N, sum P*T, sum P, sum T (int64, order-independent atomics) ----
@@ -509,6 +633,56 @@ __global__ __launch_bounds__(256) void lccb_write_kernel(const long long* __rest
     }
 }
 
+// per-class forms (see lcc_select_classes_kernel): the control words of case k are the k-th group of C in each of the three
+// runs of K * C words
+template <bool STATS>
+__global__ __launch_bounds__(256) void lccb_select_classes_kernel(Cases g, const int* __restrict__ parent,
+                                                                  const int* __restrict__ area, int C,
+                                                                  unsigned long long* __restrict__ ctrl) {
+    const int k = blockIdx.y, K = gridDim.y;
+    int s0, ns;
+    case_range(g.start, k, g.S_total, s0, ns);
+    const long hw = (long)g.H * g.W;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    ClassAcc a = {};
+    if (p < hw) {
+        const int first = (int)(s0 * hw + p * ns);
+        for (int s = 0; s < ns; ++s) {
+            const int i = first + s;
+            if (parent[i] != i) continue;
+            const int c = class_of(g.v[(long)(s0 + s) * hw + p], C);
+            if (c) class_add<STATS>(a, c, i, area[i]);
+        }
+    }
+    class_commit<STATS>(a, C, ctrl + (long)k * C, ctrl + (long)(K + k) * C, ctrl + (long)(2 * K + k) * C);
+}
+
+__global__ __launch_bounds__(256) void lccb_write_classes_kernel(Cases g, const int* __restrict__ parent, int C,
+                                                                 const unsigned long long* __restrict__ ctrl,
+                                                                 unsigned char* __restrict__ out, long long* __restrict__ stats) {
+    __shared__ int best[MAXC];
+    const int k = blockIdx.y, K = gridDim.y;
+    const unsigned long long* keys = ctrl + (long)k * C;
+    class_best(keys, C, best);
+    if (stats && blockIdx.x == 0)
+        class_stats(keys, ctrl + (long)(K + k) * C, ctrl + (long)(2 * K + k) * C, C, stats + (long)k * C * 3);
+    int s0, ns;
+    case_range(g.start, k, g.S_total, s0, ns);
+    const long hw = (long)g.H * g.W;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= hw) return;
+    const int first = (int)(s0 * hw + p * ns);
+    for (int s = 0; s < ns; ++s) {
+        const int q = parent[first + s];
+        int o = 0;
+        if (q >= 0) {
+            const int c = class_of(g.v[(long)(s0 + s) * hw + p], C);
+            if (c && best[c] >= 0 && find_plain(parent, q) == best[c]) o = c;
+        }
+        out[(long)(s0 + s) * hw + p] = (unsigned char)o;
+    }
+}
+
 // out[k][0..3] = N, sum p*t, sum p, sum t with t = (target byte == match); VEC: 16 bytes per load (hw % 16 == 0, aligned)
 template <bool VEC>
 __global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned char* __restrict__ p,
@@ -605,6 +779,51 @@ int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d
     return aide_launch_status();
 }
 
+size_t aide_lcc3d_classes_ws_bytes(int64_t nvox, int num_classes) {
+    if (nvox < 0 || nvox > INT32_MAX || num_classes < 2 || num_classes > MAXC) return 0;
+    return (size_t)(2 * nvox) * sizeof(int) + 16 + (size_t)(3 * num_classes) * sizeof(unsigned long long);
+}
+
+// launches 1 - 3 are the binary form's, unchanged; one memset clears the 3 C control words before them
+int aide_keep_largest_cc3d_classes(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                                   int num_classes, unsigned char* out, long long* stats, void* ws, hipStream_t stream) {
+    if (num_classes < 2 || num_classes > MAXC || !dims_ok(d0, d1, d2)) return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2), C = num_classes;
+    if (n == 0) {
+        if (!stats) return 0;
+        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * C) * sizeof(long long), stream);
+    }
+    if (!v || !out || !ws) return AIDE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    int* parent = static_cast<int*>(ws);
+    int* area = parent + n;
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    Vol g;
+    g.v = v; g.s0 = (long)s0; g.s1 = (long)s1; g.s2 = (long)s2;
+    g.d0 = (int)d0; g.d1 = (int)d1; g.d2 = (int)d2;
+    g.tx = (int)((d2 + TX - 1) / TX); g.ty = (int)((d1 + TY - 1) / TY);
+    const long tiles = (long)g.tx * g.ty * ((d0 + TZ - 1) / TZ);
+    const unsigned nb = (unsigned)(((long)n + 255) / 256);
+    const unsigned ntile = (unsigned)min(tiles, 65536L);
+    const unsigned nsel = (unsigned)min((long)nb, 1024L);
+    hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(3 * C) * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return (int)e;
+    const double bytes = 29.0 * n;
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel, dim3(nb), dim3(256), 0, stream, parent, area, n);
+    if (stats)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_classes_kernel<true>, dim3(nsel), dim3(256), 0, stream, g,
+                          (const int*)parent, (const int*)area, n, C, ctrl);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_classes_kernel<false>, dim3(nsel), dim3(256), 0, stream, g,
+                          (const int*)parent, (const int*)area, n, C, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_write_classes_kernel, dim3(nb), dim3(256), 0, stream, g, (const int*)parent, n, C,
+                      (const unsigned long long*)ctrl, out, stats);
+    return aide_launch_status();
+}
+
 int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
                         int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, long long* out,
                         hipStream_t stream) {
@@ -658,6 +877,49 @@ int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_st
                       ctrl);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_write_kernel, gc, block, 0, stream, slice_start, (int)S_total, (long)hw,
                       (const int*)parent, (const unsigned long long*)ctrl, out);
+    return aide_launch_status();
+}
+
+size_t aide_lcc3d_classes_batched_ws_bytes(int64_t nvox_total, int64_t K, int num_classes) {
+    if (nvox_total < 0 || nvox_total > INT32_MAX || K < 0 || K > 65535 || num_classes < 2 || num_classes > MAXC) return 0;
+    return (size_t)(2 * nvox_total) * sizeof(int) + 16 + (size_t)(3 * K * num_classes) * sizeof(unsigned long long);
+}
+
+int aide_keep_largest_cc3d_classes_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total,
+                                           int64_t H, int64_t W, int num_classes, unsigned char* out, long long* stats,
+                                           void* ws, hipStream_t stream) {
+    if (num_classes < 2 || num_classes > MAXC || !batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
+    const int n = (int)(S_total * H * W), C = num_classes;
+    if (n == 0 || K == 0) {
+        if (!stats || K == 0) return 0;
+        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * K * C) * sizeof(long long), stream);
+    }
+    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    int* parent = static_cast<int*>(ws);
+    int* area = parent + n;
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    Cases g;
+    g.v = v; g.start = slice_start; g.S_total = (int)S_total; g.H = (int)H; g.W = (int)W;
+    g.tw = (int)((W + 15) / 16);
+    const long tiles = (long)g.tw * ((H + 15) / 16), chunks = (H * W + 255) / 256;
+    if (tiles > INT32_MAX) return AIDE_ERR_ARG;
+    const dim3 gt((unsigned)tiles, (unsigned)K), gc((unsigned)chunks, (unsigned)K), block(256);
+    const int hw = (int)(H * W);
+    hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(3 * K * C) * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return (int)e;
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 29.0 * n, lccb_local_kernel, gt, block, 0, stream, g, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_border_kernel, gt, block, 0, stream, g, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_count_kernel, gc, block, 0, stream, slice_start, (int)S_total, hw, parent, area);
+    if (stats)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_classes_kernel<true>, gc, block, 0, stream, g, (const int*)parent,
+                          (const int*)area, C, ctrl);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_classes_kernel<false>, gc, block, 0, stream, g, (const int*)parent,
+                          (const int*)area, C, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_write_classes_kernel, gc, block, 0, stream, g, (const int*)parent, C,
+                      (const unsigned long long*)ctrl, out, stats);
     return aide_launch_status();
 }
 

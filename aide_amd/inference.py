@@ -56,11 +56,25 @@ def predict_labels(net, *modal_inputs, **kw):
 def predict_case(net, *modal_inputs, **kw):
     """The reference's `generatedtarget`: numpy int64 [H,W,S] (slices stacked on the last axis, :267).
     keep_largest=True: its largest connected component (:268), uint8, filtered on the device before anything leaves it.
+    keep_largest='per_class' with num_classes=C: the largest component of every class 1 .. C - 1 (`keep_largest_per_class`),
+    uint8 class values, for multi-organ networks.
     numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered)."""
     keep_largest = kw.pop('keep_largest', False)
+    num_classes = kw.pop('num_classes', None)
     as_numpy = kw.pop('numpy', True)
+    per_class = isinstance(keep_largest, str)
+    if per_class:
+        if keep_largest != 'per_class':
+            raise ValueError("keep_largest must be True, False or 'per_class', got %r" % (keep_largest,))
+        if num_classes is None:
+            raise TypeError("predict_case: keep_largest='per_class' needs num_classes")
+        num_classes = _num_classes(num_classes, 'predict_case')
+    elif num_classes is not None:
+        raise TypeError("predict_case: num_classes goes with keep_largest='per_class'")
     vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
-    if keep_largest:
+    if per_class:
+        vol = keep_largest_per_class(vol, num_classes)
+    elif keep_largest:
         vol = keep_largest_connected_components(vol)
     if not as_numpy:
         return vol
@@ -139,6 +153,69 @@ def _keep_largest_device(mask):
     check(lib.aide_keep_largest_cc3d(ptr(mask), *mask.shape, *mask.stride(), ptr(out), ptr(ws), stream_ptr()),
           'keep_largest_cc3d')
     return out
+
+
+def _num_classes(c, what):
+    c = int(c)
+    if not 2 <= c <= 8:
+        raise RuntimeError('%s: num_classes %d, 2 .. 8 are supported' % (what, c))
+    return c
+
+
+def keep_largest_per_class(mask, num_classes, stats=False):
+    """The filter for multi-organ volumes (the reference has one blob for the whole volume, which keeps the liver of a CHAOS
+    prediction and deletes the kidneys and the spleen): for every class value c in 1 .. num_classes - 1 the largest blob of
+    the voxels equal to c (connectivity 1; a tie goes to the blob whose first voxel comes first in raster order of the logical
+    index, the rule of `keep_largest_connected_components` per class).  uint8 volume of the same shape: c on the kept blob
+    of class c, 0 elsewhere; a value outside 1 .. num_classes - 1 belongs to no class; a class that does not occur leaves
+    nothing.  num_classes = 2 on a {0, 1} volume is `keep_largest_connected_components`, byte for byte.
+    stats=True: also int64 [num_classes, 3], row c = (blobs of class c, voxels of class c, voxels of the kept blob), row 0
+    zeros.  HIP integer tensor of any strides: `aide_keep_largest_cc3d_classes`, five launches and one memset, asynchronous,
+    HIP tensors returned.  numpy array or CPU tensor: scipy.ndimage.label once per class, numpy arrays returned."""
+    c = _num_classes(num_classes, 'keep_largest_per_class')
+    if isinstance(mask, torch.Tensor) and mask.is_cuda:
+        out, st = _keep_largest_classes_device(mask, c, stats)
+    else:
+        if isinstance(mask, torch.Tensor):
+            mask = mask.detach().numpy()
+        out, st = _keep_largest_classes_host(np.asarray(mask), c)
+    return (out, st) if stats else out
+
+
+def _keep_largest_classes_host(mask, c):
+    from scipy import ndimage
+    out = np.zeros(mask.shape, dtype=np.uint8)
+    st = np.zeros((c, 3), dtype=np.int64)
+    if mask.size == 0:
+        return out, st
+    for v in range(1, c):
+        blobs, count = ndimage.label(mask == v)
+        if count == 0:
+            continue
+        flat = blobs.reshape(-1)
+        area = np.bincount(flat, minlength=count + 1)[1:]
+        first = np.full(count + 1, flat.size, dtype=np.int64)
+        idx = np.flatnonzero(flat)
+        np.minimum.at(first, flat[idx], idx)
+        b = max(range(count), key=lambda j: (int(area[j]), -int(first[j + 1])))
+        out[blobs == b + 1] = v
+        st[v] = count, int(area.sum()), int(area[b])
+    return out, st
+
+
+def _keep_largest_classes_device(mask, c, stats):
+    _lcc_args(mask)
+    mask = mask.detach()
+    if mask.dtype != torch.int64:
+        mask = mask.to(torch.int64)
+    out = torch.empty(mask.shape, device=mask.device, dtype=torch.uint8)
+    st = torch.empty(c, 3, device=mask.device, dtype=torch.int64) if stats else None
+    if mask.numel() == 0:
+        return out, (st.zero_() if stats else None)
+    ws = torch.empty(lib.aide_lcc3d_classes_ws_bytes(mask.numel(), c), device=mask.device, dtype=torch.uint8)
+    check(lib.aide_keep_largest_cc3d_classes(ptr(mask), *mask.shape, *mask.stride(), c, ptr(out), ptr(st), ptr(ws),
+                                             stream_ptr()), 'keep_largest_cc3d_classes')
+    return out, st
 
 
 def _confusion_args(pred, target):
@@ -266,10 +343,15 @@ def _starts(slice_start, s_total):
     return st
 
 
-def keep_largest_batched(labels, slice_start):
+def keep_largest_batched(labels, slice_start, num_classes=None, stats=False):
     """[S_total,H,W] integer label maps of K concatenated cases + slice_start[K+1] -> uint8 [S_total,H,W]: for every case
     what `keep_largest_connected_components` gives for its [H,W,S_k] volume.  HIP tensors (slice_start an int64 HIP tensor:
-    the table is not read on the host): five launches for any K, no synchronisation.  Anything else: the CPU function per case."""
+    the table is not read on the host): five launches for any K, no synchronisation.  Anything else: the CPU function per case.
+    num_classes=C (2 .. 8): per case what `keep_largest_per_class` gives instead (`aide_keep_largest_cc3d_classes_batched`:
+    five launches and one memset for any K and C); stats=True then also returns int64 [K, C, 3], the per-case rows."""
+    c = None if num_classes is None else _num_classes(num_classes, 'keep_largest_batched')
+    if stats and c is None:
+        raise TypeError('keep_largest_batched: stats needs num_classes')
     if isinstance(labels, torch.Tensor) and labels.is_cuda:
         if labels.dim() != 3 or labels.dtype not in _INT_DTYPES:
             raise RuntimeError('keep_largest_batched: [S,H,W] integer labels expected')
@@ -281,6 +363,14 @@ def keep_largest_batched(labels, slice_start):
         v = labels.detach().to(torch.int64).contiguous()
         k = slice_start.numel() - 1
         out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
+        if c is not None:
+            st = torch.empty(k, c, 3, device=v.device, dtype=torch.int64) if stats else None
+            if v.numel() == 0 or k == 0:
+                return (out.zero_(), st.zero_()) if stats else out.zero_()
+            ws = torch.empty(lib.aide_lcc3d_classes_batched_ws_bytes(v.numel(), k, c), device=v.device, dtype=torch.uint8)
+            check(lib.aide_keep_largest_cc3d_classes_batched(ptr(v), ptr(slice_start), k, *v.shape, c, ptr(out), ptr(st),
+                                                             ptr(ws), stream_ptr()), 'keep_largest_cc3d_classes_batched')
+            return (out, st) if stats else out
         if v.numel() == 0 or k == 0:
             return out.zero_()
         ws = torch.empty(lib.aide_lcc3d_batched_ws_bytes(v.numel(), k), device=v.device, dtype=torch.uint8)
@@ -290,6 +380,13 @@ def keep_largest_batched(labels, slice_start):
     lab = np.asarray(labels)
     st = _starts(slice_start, lab.shape[0])
     out = np.zeros(lab.shape, np.uint8)
+    if c is not None:
+        rows = np.zeros((len(st) - 1, c, 3), np.int64)
+        for k, (a, b) in enumerate(zip(st, st[1:])):
+            if b > a:
+                keep, rows[k] = _keep_largest_classes_host(lab[a:b].transpose(1, 2, 0), c)
+                out[a:b] = keep.transpose(2, 0, 1)
+        return (out, rows) if stats else out
     for a, b in zip(st, st[1:]):
         if b > a:
             out[a:b] = keep_largest_connected_components(lab[a:b].transpose(1, 2, 0)).transpose(2, 0, 1)

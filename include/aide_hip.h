@@ -556,6 +556,22 @@ size_t aide_lcc3d_ws_bytes(int64_t nvox);
  * order; all zeros when the volume has no positive value.  d0 * d1 * d2 < 2^31 (AIDE_ERR_ARG otherwise). */
 int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
                            unsigned char* out, void* ws, aide_stream_t stream);
+/* workspace of aide_keep_largest_cc3d_classes (16-byte aligned); 0 for nvox >= 2^31 or num_classes outside 2 .. 8 */
+size_t aide_lcc3d_classes_ws_bytes(int64_t nvox, int num_classes);
+/* The filter per class for multi-organ volumes, C = num_classes in 2 .. 8: for every class value c in 1 .. C - 1 the largest
+ * blob of the voxels equal to c (face neighbours, ties to the blob whose first voxel comes first in raster order, the rule
+ * above applied per class; classes never compete).  out[d0][d1][d2] (uint8, contiguous) = c on the kept blob of class c, 0
+ * elsewhere; a value outside 1 .. C - 1 (0, negative, >= C) belongs to no class and gives 0; a class that does not occur
+ * leaves nothing.  For C = 2 and values in {0, 1} the bytes are aide_keep_largest_cc3d's.
+ * stats: NULL, or [C][3] int64: row c = {blobs of class c, voxels of class c, voxels of the kept blob}, row 0 zeros.
+ * Five launches (the first three are aide_keep_largest_cc3d's) and one memset of the control words, whatever C is; integer
+ * only, so two calls give the same bytes whatever the workspace held.  AIDE_ERR_ARG before any launch for a null v / out /
+ * ws, a misaligned ws, d0 * d1 * d2 >= 2^31, num_classes outside 2 .. 8; an empty volume launches nothing (stats, when
+ * given, is cleared). */
+int aide_keep_largest_cc3d_classes(const long long* v, int64_t d0, int64_t d1, int64_t d2,
+                                   int64_t s0, int64_t s1, int64_t s2, int num_classes,
+                                   unsigned char* out, long long* stats /* NULL or [C][3] */,
+                                   void* ws, aide_stream_t stream);
 /* out[4] (int64) = {N, sum p*t, sum p, sum t} over the logical volume; p / t are int64 (x_u8 = 0) or uint8 (x_u8 = 1)
  * with element strides.  TP = out[1], FP = out[2] - out[1], FN = out[3] - out[1], TN = N - out[2] - out[3] + out[1] */
 int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
@@ -595,6 +611,16 @@ size_t aide_lcc3d_batched_ws_bytes(int64_t nvox_total, int64_t K);
  * a positive value.  Slices that belong to no case are not written.  Five launches. */
 int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H,
                                    int64_t W, unsigned char* out, void* ws, aide_stream_t stream);
+/* workspace of aide_keep_largest_cc3d_classes_batched (16-byte aligned); 0 when the arguments are out of range */
+size_t aide_lcc3d_classes_batched_ws_bytes(int64_t nvox_total, int64_t K, int num_classes);
+/* out[S_total][H][W] (uint8) = per case what aide_keep_largest_cc3d_classes gives for that case alone: one selection key per
+ * (case, class), the tie rule within the case's raster order.  stats: NULL, or [K][C][3] int64, per case the rows of the
+ * single-volume form (all zeros for an empty case).  Slices that belong to no case are not written.  Five launches and one
+ * memset, whatever K and C are.  AIDE_ERR_ARG as for the two forms it combines. */
+int aide_keep_largest_cc3d_classes_batched(const long long* v, const long long* slice_start, int64_t K,
+                                           int64_t S_total, int64_t H, int64_t W, int num_classes,
+                                           unsigned char* out, long long* stats /* NULL or [K][C][3] */,
+                                           void* ws, aide_stream_t stream);
 /* out[K][4] (int64) = {N, sum p*t, sum p, sum t} per case with t = (target byte == match): p is the uint8 prediction, target
  * a plane of the pseudo-label bank (match 63: the CHAOS liver plane mask[1] of the loader's palette one-hot).  One launch. */
 int aide_case_confusion_batched(const unsigned char* p, const unsigned char* target, const long long* slice_start, int64_t K,
