@@ -21,9 +21,17 @@
 // (inf + x = inf, min keeps the finite side, no product has an infinite factor: the spacings are finite); launch 4 takes a
 // square root only of a finite minimum, which exists for every voxel as soon as the other operand has one border voxel.
 // All indices come from integers.
+//
+// aide_surface3d_scores_select (percentiles of the distances and counts within a tolerance: HD95, NSD) runs the same launches
+// with launch 4 as surf_minplus<true, true>, which also appends every distance to a per-operand list of uint64 keys, and then
+// 8 x (sel_hist, sel_choose): an exact MSD radix select over those lists for all (set, rank) targets at once -- see there.
+// Integer atomics only; the lists' order depends on the schedule and nothing computed from them does.
 #include "common.h"
 
 #include <cmath>
+#include <cstring>
+
+extern "C" size_t aide_surface3d_ws_bytes(int64_t nvox);
 
 namespace {
 
@@ -106,10 +114,15 @@ struct Lines {
 
 // !LAST: f[op] from g[op].  LAST (blockIdx.y = op: 0 measures the border voxels of P against T, 1 the reverse):
 // dist[op][i] = sqrt(min) at the border voxels of operand op against f[1 - op], -1 elsewhere; part[op][blockIdx.x] = {sum, max}
-template <bool LAST>
+// KEYS (LAST only; aide_surface3d_scores_select): every distance is also appended to keys[op][kcnt[op]++] as its bit pattern,
+// which orders like the non-negative double.  A wave takes the slots of the up to R * 64 distances of a chunk with one integer
+// atomic (ballots, popcounts, lane prefix), so the order of the list depends on the schedule; the sum and the max do not.
+template <bool LAST, bool KEYS = false>
 __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* __restrict__ g, double* __restrict__ f,
                                                            const unsigned char* __restrict__ bmap,
-                                                           double* __restrict__ dist, double* __restrict__ part) {
+                                                           double* __restrict__ dist, double* __restrict__ part,
+                                                           unsigned long long* __restrict__ keys = nullptr,
+                                                           unsigned* __restrict__ kcnt = nullptr) {
     __shared__ double h[CH][COLS];
     __shared__ double red[2][256];
     const int op = blockIdx.y, col = threadIdx.x & 63, row = threadIdx.x >> 6;
@@ -154,18 +167,43 @@ __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* _
             }
         }
         if (LAST) {
+            double dk[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int i = first + r;
-                if (!live || i >= q.L) continue;
-                const size_t at = dst + (size_t)i * q.stride;
                 double d = -1.0;
-                if (bmap[at] && best[r] < inf) {
-                    d = sqrt(best[r]);
-                    sum += d;
-                    mx = fmax(mx, d);
+                if (live && i < q.L) {
+                    const size_t at = dst + (size_t)i * q.stride;
+                    if (bmap[at] && best[r] < inf) {
+                        d = sqrt(best[r]);
+                        sum += d;
+                        mx = fmax(mx, d);
+                    }
+                    if (dist) dist[at] = d;
                 }
-                if (dist) dist[at] = d;
+                dk[r] = d;
+            }
+            if constexpr (KEYS) {                // whole waves arrive here: no thread has left the kernel
+                unsigned long long has[R];
+                unsigned total = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    has[r] = __ballot(dk[r] >= 0.0);
+                    total += (unsigned)__popcll(has[r]);
+                }
+                if (total) {                     // wave-uniform
+                    unsigned base = 0;
+                    if (col == 0) base = atomicAdd(kcnt + op, total);
+                    base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                    const unsigned long long below = (1ull << col) - 1ull;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const unsigned slot = base + (unsigned)__popcll(has[r] & below);
+                        if (dk[r] >= 0.0 && slot < (unsigned)q.n)      // (at most n_op <= n distances exist)
+                            keys[(size_t)op * q.n + slot] = (unsigned long long)__double_as_longlong(dk[r]);
+                        base += (unsigned)__popcll(has[r]);
+                    }
+                }
             }
         } else {
 #pragma unroll
@@ -223,6 +261,136 @@ __global__ __launch_bounds__(256) void surf_finish_kernel(const double* __restri
     }
 }
 
+// ---- exact selection over the key lists (aide_surface3d_scores_select) --------------------------------------------------------
+// A target = (set, rank): set 0 = A (keys[0]), 1 = B (keys[1]), 2 = the multiset union; target index t = set * 8 + 2 * j + h for
+// percentile j < nq, h = 0: rank lo, h = 1: rank hi.  MSD radix select, 8 passes of 8 bits: sel_hist counts, per target, the
+// digits of the keys whose higher digits equal the target's prefix; sel_choose (one workgroup per target) walks the 256 bins,
+// picks the digit that holds the rank, extends the prefix, reduces the rank to one inside that digit and clears the bins for
+// the next pass.  After pass 7 the prefix is the key of that rank.  Equal keys share every digit: a run of ties is one bin.
+constexpr int SEL_T = 24;          // targets: 3 sets x 4 percentiles x {lo, hi}
+constexpr int SEL_WG = 512;        // workgroups per operand of sel_hist (grid-stride over the list)
+
+struct SelState {
+    unsigned long long prefix;     // the digits chosen so far, right-aligned
+    unsigned long long rank;       // rank among the keys that carry the prefix
+};
+
+struct SelArgs {
+    double q[4];
+    unsigned long long tol[4];     // bit patterns of the tolerances
+    int nq, nt;
+};
+
+// bins[d] += 1 for the active lanes of a wave.  The largest group of equal digits is the rule, not the exception (every key
+// shares its exponent bits with most others; at unit spacing thousands of keys are equal), so the group of the first active
+// lane goes as one add of its size; the others add one each.
+__device__ __forceinline__ void sel_count(unsigned* bins, bool active, unsigned digit, int lane) {
+    const unsigned long long m = __ballot(active);
+    if (m) {
+        const int lead = __ffsll((long long)m) - 1;
+        const unsigned ld = (unsigned)__builtin_amdgcn_readlane((int)digit, lead);
+        const unsigned long long grp = __ballot(active && digit == ld);
+        if (lane == lead) atomicAdd(bins + ld, (unsigned)__popcll(grp));
+        if (active && digit != ld) atomicAdd(bins + digit, 1u);
+    }
+}
+
+// grid (SEL_WG, 2): blockIdx.y = the list.  PASS 0 also counts the keys <= tol[j] into out[8 + 2 * j + op].
+template <int PASS>
+__global__ __launch_bounds__(256) void sel_hist_kernel(SelArgs a, int n, const unsigned long long* __restrict__ keys,
+                                                       const unsigned* __restrict__ kcnt, const SelState* __restrict__ st,
+                                                       unsigned* __restrict__ hist, unsigned long long* __restrict__ out) {
+    __shared__ unsigned h[SEL_T][256];
+    __shared__ unsigned long long pre[SEL_T];
+    const int op = blockIdx.y, lane = threadIdx.x & 63;
+    const unsigned cnt = min(kcnt[op], (unsigned)n);
+    if (blockIdx.x * 256u >= cnt) return;                                  // block-uniform: nothing of the list is mine
+    const int nper = 2 * a.nq;                                             // targets per set
+    for (int i = threadIdx.x; i < SEL_T * 256; i += 256) (&h[0][0])[i] = 0u;
+    if (threadIdx.x < SEL_T) pre[threadIdx.x] = PASS ? st[threadIdx.x].prefix : 0ull;
+    __syncthreads();
+    constexpr int shift = 56 - 8 * PASS;
+    const unsigned long long* list = keys + (size_t)op * n;
+    unsigned within[4] = {0u, 0u, 0u, 0u};                                 // wave-uniform
+    const unsigned rounds = (cnt + 255u) / 256u;                           // whole waves walk every round
+    for (unsigned k = blockIdx.x; k < rounds; k += gridDim.x) {
+        const unsigned i = k * 256u + threadIdx.x;
+        const bool ok = i < cnt;
+        const unsigned long long key = ok ? list[i] : 0ull;
+        const unsigned digit = (unsigned)(key >> shift) & 255u;
+        unsigned long long high = 0ull;                                    // the digits above this pass's
+        if constexpr (PASS > 0) high = key >> (shift + 8);
+        for (int s = op; s < 3; s += 2 - op) {                             // the sets this list belongs to: op and 2
+            for (int j = 0; j < nper; ++j) {
+                const int t = s * 8 + j;
+                sel_count(h[t], ok && high == pre[t], digit, lane);
+            }
+        }
+        if (PASS == 0) {
+            for (int j = 0; j < a.nt; ++j) within[j] += (unsigned)__popcll(__ballot(ok && key <= a.tol[j]));
+        }
+    }
+    __syncthreads();
+    for (int s = op; s < 3; s += 2 - op) {
+        for (int j = 0; j < nper; ++j) {
+            const int t = s * 8 + j;
+            const unsigned v = h[t][threadIdx.x];
+            if (v) atomicAdd(hist + t * 256 + threadIdx.x, v);
+        }
+    }
+    if (PASS == 0 && lane == 0) {
+        for (int j = 0; j < a.nt; ++j)
+            if (within[j]) atomicAdd(out + 8 + 2 * j + op, (unsigned long long)within[j]);
+    }
+}
+
+// grid (SEL_T): one workgroup per target, thread d owns bin d.  PASS 0 derives the rank from n_P = out[0], n_T = out[1] and q
+// (pos = (m - 1) * q / 100.0 left to right in fp64: a product and a quotient, nothing to contract) and writes lo; pass 7 writes
+// the key.  A rank that no bin holds (a list shorter than its border count: include/aide_hip.h on overflow) takes digit 255.
+template <int PASS>
+__global__ __launch_bounds__(256) void sel_choose_kernel(SelArgs a, SelState* __restrict__ st, unsigned* __restrict__ hist,
+                                                         unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long scan[256];
+    __shared__ unsigned long long found[2];                                // digit, rank inside it
+    const int t = blockIdx.x, s = t >> 3, j = (t & 7) >> 1, hi = t & 1, d = threadIdx.x;
+    if (j >= a.nq) return;
+    const long long n_p = (long long)out[0], n_t = (long long)out[1];
+    const bool valid = n_p > 0 && n_t > 0;
+    unsigned long long prefix = 0ull, rank = 0ull;
+    if (PASS == 0) {
+        if (valid) {
+            const long long m = s == 0 ? n_p : s == 1 ? n_t : n_p + n_t;
+            const double pos = (double)(m - 1) * a.q[j] / 100.0;
+            const long long lo = (long long)floor(pos);
+            rank = (unsigned long long)(hi ? (lo + 1 < m - 1 ? lo + 1 : m - 1) : lo);
+            if (!hi && d == 0) out[16 + 3 * (s * 4 + j)] = (unsigned long long)lo;
+        }
+    } else {
+        prefix = st[t].prefix;
+        rank = st[t].rank;
+    }
+    const unsigned mine = hist[t * 256 + d];
+    hist[t * 256 + d] = 0u;                                                // the next pass starts from cleared bins
+    scan[d] = mine;
+    if (d == 0) { found[0] = 255ull; found[1] = rank; }
+    __syncthreads();
+    for (int w = 1; w < 256; w <<= 1) {                                    // inclusive scan
+        const unsigned long long add = d >= w ? scan[d - w] : 0ull;
+        __syncthreads();
+        scan[d] += add;
+        __syncthreads();
+    }
+    const unsigned long long incl = scan[d], excl = incl - mine;
+    if (excl <= rank && rank < incl) { found[0] = (unsigned long long)d; found[1] = rank - excl; }   // at most one thread
+    __syncthreads();
+    if (d == 0) {
+        prefix = (prefix << 8) | found[0];
+        st[t].prefix = prefix;
+        st[t].rank = found[1];
+        if (PASS == 7) out[16 + 3 * (s * 4 + j) + 1 + hi] = valid ? prefix : 0ull;
+    }
+}
+
 bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
     if (d0 < 0 || d1 < 0 || d2 < 0) return false;
     if (d0 == 0 || d1 == 0 || d2 == 0) return true;
@@ -231,21 +399,21 @@ bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-}  // namespace
+constexpr int SEL_WORDS = 52;      // out of aide_surface3d_scores_select, in words of 8 bytes
+constexpr size_t SEL_CTRL_BYTES = 16 + SEL_T * sizeof(SelState) + SEL_T * 256 * sizeof(unsigned);
 
-extern "C" {
-
-// f [2][n] fp64 | g [2][n] int32 | bmap [2][n] bytes | slots [2][ceil(n / 64)][2] fp64 (d1 * d2 <= n: as many as any shape needs)
-size_t aide_surface3d_ws_bytes(int64_t nvox) {
-    if (nvox < 0 || nvox > INT32_MAX) return 0;
-    const size_t n = (size_t)nvox;
-    const size_t slots = (n + COLS - 1) / COLS;
-    return align16(2 * n * sizeof(double)) + align16(2 * n * sizeof(int)) + align16(2 * n) + 4 * slots * sizeof(double) + 16;
+template <int PASS>
+void sel_pass(const SelArgs& a, int n, const unsigned long long* keys, const unsigned* kcnt, SelState* state, unsigned* hist,
+              unsigned long long* out, hipStream_t stream) {
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, sel_hist_kernel<PASS>, dim3(SEL_WG, 2), dim3(256), 0, stream, a, n, keys, kcnt,
+                      (const SelState*)state, hist, out);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, sel_choose_kernel<PASS>, dim3(SEL_T), dim3(256), 0, stream, a, state, hist, out);
 }
 
-int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
-                          int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1,
-                          double sp2, int cls, void* out, double* dist, void* ws, hipStream_t stream) {
+// the launches of both entry points; sel = nullptr: aide_surface3d_scores
+int surface_run(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8, int64_t t_s0,
+                int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1, double sp2, int cls,
+                const SelArgs* sel, void* out, double* dist, void* ws, hipStream_t stream) {
     if (!dims_ok(d0, d1, d2) || !p || !t || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
     if ((p_u8 != 0 && p_u8 != 1) || (t_u8 != 0 && t_u8 != 1)) return AIDE_ERR_ARG;
     if (!(sp0 > 0.0 && sp1 > 0.0 && sp2 > 0.0) || !std::isfinite(sp0) || !std::isfinite(sp1) || !std::isfinite(sp2))
@@ -254,7 +422,7 @@ int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, i
     const int plane = (int)(d1 * d2);
     const long cols1 = (long)d0 * d2, cols0 = plane;                        // lines along d1, along d0
     const long slots = (cols0 + COLS - 1) / COLS;
-    hipError_t e = hipMemsetAsync(out, 0, 8 * sizeof(double), stream);
+    hipError_t e = hipMemsetAsync(out, 0, (sel ? SEL_WORDS : 8) * sizeof(double), stream);
     if (e != hipSuccess) return (int)e;
     if (n == 0) return 0;
     char* w = static_cast<char*>(ws);
@@ -274,18 +442,98 @@ int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, i
     a0.L = (int)d0; a0.stride = plane; a0.inner = plane; a0.outer = 0; a0.ncol = (int)cols0; a0.n = n;
     a0.sp = sp0; a0.sp_in = 0.0;
     const dim3 block(256);
+    unsigned long long* keys = nullptr;
+    unsigned* kcnt = nullptr;
+    SelState* state = nullptr;
+    unsigned* hist = nullptr;
     const double bytes_in = (double)n * ((p_u8 ? 1 : 8) + (t_u8 ? 1 : 8));
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes_in + 2.0 * n, surf_border_kernel, dim3(nb), block, 0, stream, P, T, (int)d0, (int)d1,
                       (int)d2, n, cls, bmap, static_cast<unsigned long long*>(out));
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 10.0 * n, surf_scan2_kernel, dim3((unsigned)((lines + 255) / 256), 2), block, 0, stream,
                       (const unsigned char*)bmap, lines, (int)d2, n, g);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 24.0 * n, surf_minplus_kernel<false>, dim3((unsigned)((cols1 + COLS - 1) / COLS), 2), block,
-                      0, stream, a1, (const int*)g, f, (const unsigned char*)bmap, (double*)nullptr, (double*)nullptr);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (dist ? 34.0 : 18.0) * n, surf_minplus_kernel<true>, dim3((unsigned)slots, 2), block, 0,
-                      stream, a0, (const int*)g, f, (const unsigned char*)bmap, dist, part);
+                      0, stream, a1, (const int*)g, f, (const unsigned char*)bmap, (double*)nullptr, (double*)nullptr,
+                      (unsigned long long*)nullptr, (unsigned*)nullptr);
+    if (!sel) {
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (dist ? 34.0 : 18.0) * n, surf_minplus_kernel<true>, dim3((unsigned)slots, 2), block, 0,
+                          stream, a0, (const int*)g, f, (const unsigned char*)bmap, dist, part, (unsigned long long*)nullptr,
+                          (unsigned*)nullptr);
+    } else {
+        char* w2 = static_cast<char*>(ws) + aide_surface3d_ws_bytes(n);
+        keys = reinterpret_cast<unsigned long long*>(w2);
+        w2 += 2 * (size_t)n * sizeof(unsigned long long);
+        kcnt = reinterpret_cast<unsigned*>(w2);
+        state = reinterpret_cast<SelState*>(w2 + 16);
+        hist = reinterpret_cast<unsigned*>(w2 + 16 + SEL_T * sizeof(SelState));
+        e = hipMemsetAsync(kcnt, 0, SEL_CTRL_BYTES, stream);
+        if (e != hipSuccess) return (int)e;
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (dist ? 34.0 : 18.0) * n, (surf_minplus_kernel<true, true>), dim3((unsigned)slots, 2),
+                          block, 0, stream, a0, (const int*)g, f, (const unsigned char*)bmap, dist, part, keys, kcnt);
+    }
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, surf_finish_kernel, dim3(1), block, 0, stream, (const double*)part, (int)slots,
                       static_cast<double*>(out));
+    if (sel) {
+        unsigned long long* o = static_cast<unsigned long long*>(out);
+        sel_pass<0>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<1>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<2>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<3>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<4>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<5>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<6>(*sel, n, keys, kcnt, state, hist, o, stream);
+        sel_pass<7>(*sel, n, keys, kcnt, state, hist, o, stream);
+    }
     return aide_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+// f [2][n] fp64 | g [2][n] int32 | bmap [2][n] bytes | slots [2][ceil(n / 64)][2] fp64 (d1 * d2 <= n: as many as any shape needs)
+size_t aide_surface3d_ws_bytes(int64_t nvox) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    const size_t n = (size_t)nvox;
+    const size_t slots = (n + COLS - 1) / COLS;
+    return align16(2 * n * sizeof(double)) + align16(2 * n * sizeof(int)) + align16(2 * n) + 4 * slots * sizeof(double) + 16;
+}
+
+int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                          int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1,
+                          double sp2, int cls, void* out, double* dist, void* ws, hipStream_t stream) {
+    return surface_run(p, p_u8, p_s0, p_s1, p_s2, t, t_u8, t_s0, t_s1, t_s2, d0, d1, d2, sp0, sp1, sp2, cls, nullptr, out, dist, ws,
+                       stream);
+}
+
+// the workspace of aide_surface3d_scores | keys [2][n] uint64 | control: kcnt [2] uint32 (+ pad), state [24], bins [24][256]
+size_t aide_surface3d_select_ws_bytes(int64_t nvox) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    return aide_surface3d_ws_bytes(nvox) + 2 * (size_t)nvox * sizeof(unsigned long long) + SEL_CTRL_BYTES;
+}
+
+int aide_surface3d_scores_select(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
+                                 int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, double sp0,
+                                 double sp1, double sp2, int cls, const double* q, int nq, const double* tol, int nt, void* out,
+                                 double* dist, void* ws, hipStream_t stream) {
+    if (nq < 0 || nq > 4 || nt < 0 || nt > 4 || (nq && !q) || (nt && !tol)) return AIDE_ERR_ARG;
+    SelArgs a;
+    a.nq = nq;
+    a.nt = nt;
+    for (int j = 0; j < 4; ++j) {
+        a.q[j] = 0.0;
+        a.tol[j] = 0ull;
+    }
+    for (int j = 0; j < nq; ++j) {
+        if (!std::isfinite(q[j]) || q[j] < 0.0 || q[j] > 100.0) return AIDE_ERR_ARG;
+        a.q[j] = q[j];
+    }
+    for (int j = 0; j < nt; ++j) {
+        if (!std::isfinite(tol[j]) || tol[j] < 0.0) return AIDE_ERR_ARG;
+        const double v = tol[j] + 0.0;                                      // -0.0 -> +0.0: the bits must order like the value
+        memcpy(&a.tol[j], &v, sizeof v);
+    }
+    return surface_run(p, p_u8, p_s0, p_s1, p_s2, t, t_u8, t_s0, t_s1, t_s2, d0, d1, d2, sp0, sp1, sp2, cls, &a, out, dist, ws,
+                       stream);
 }
 
 }  // extern "C"

@@ -301,7 +301,7 @@ def _case_scores_classes(pred, target, c):
     return dict(Dice=dice, IoU=iou, TP=tp.copy(), TN=n - si - st + tp, FP=si - tp, FN=st - tp)
 
 
-def case_scores(pred, target, num_classes=None, spacing=None):
+def case_scores(pred, target, num_classes=None, spacing=None, percentiles=None, tolerances=None):
     """Per-case scores of the evaluation script (evalchaos_comparison_1cases.py:116-141, 238-242) for a predicted label
     volume against its target: dict(Dice, IoU, TP, TN, FP, FN).  HIP tensors: one confusion launch and one copy of four
     int64 sums to the host; anything else: the same sums in int64 on the CPU.  TP = sum p*t, FP = sum p - TP,
@@ -312,12 +312,16 @@ def case_scores(pred, target, num_classes=None, spacing=None):
     launch of aide_mc_counts_labels and one copy of C * 3 int64.
     spacing=(sp0, sp1, sp2), the edge lengths of a voxel along the three dims of the volumes (the evaluation script's
     `voxelspacing`, :181, 192-194): the dict also carries RAVD, ASSD and MSSD of `utils.metrics3d.surface_scores`; without it
-    the dict is the six scores above and nothing else."""
+    the dict is the six scores above and nothing else.
+    percentiles=(q, ...) / tolerances=(tau, ...) (1 .. 4 numbers each; they need `spacing`, TypeError without it) go to
+    `surface_scores` and add HD and HD_pooled ([Q], or [C, Q]) / NSD ([T], or [C, T]): percentiles=(95,) is HD95."""
+    if spacing is None and (percentiles is not None or tolerances is not None):
+        raise TypeError('case_scores: percentiles / tolerances are surface distances and need spacing=(sp0, sp1, sp2)')
     if spacing is not None:
         from .utils.metrics3d import surface_scores
         res = case_scores(pred, target, num_classes)
-        surf = surface_scores(pred, target, spacing, num_classes)
-        res.update((k, surf[k]) for k in ('RAVD', 'ASSD', 'MSSD'))
+        surf = surface_scores(pred, target, spacing, num_classes, percentiles=percentiles, tolerances=tolerances)
+        res.update((k, surf[k]) for k in ('RAVD', 'ASSD', 'MSSD', 'HD', 'HD_pooled', 'NSD') if k in surf)
         return res
     if num_classes is not None:
         return _case_scores_classes(pred, target, int(num_classes))

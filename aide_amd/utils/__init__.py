@@ -10,4 +10,4 @@ from .augment import reverseaug, reverse_aug_tensor  # noqa: F401
 from .loader_aug import LoaderAugment, draw_aug_params, CHAOS_PALETTE  # noqa: F401
 from .reg_loss import Pixelcoreg_Focalloss, Pixelcoreg_Focalloss_twomodel  # noqa: F401
 from .poly_lr_scheduler import PolyLR  # noqa: F401
-from .metrics3d import surface_scores, RAVD3d_fn, ASSD3d_fn, MSSD3d_fn  # noqa: F401
+from .metrics3d import surface_scores, RAVD3d_fn, ASSD3d_fn, MSSD3d_fn, HD95_fn, NSD3d_fn  # noqa: F401

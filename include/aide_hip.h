@@ -598,6 +598,37 @@ int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, i
                           const void* t, int t_u8, int64_t t_s0, int64_t t_s1, int64_t t_s2,
                           int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1, double sp2,
                           int cls, void* out, double* dist, void* ws, aide_stream_t stream);
+/* ---- percentiles of the surface distances (HD95) and the surface Dice at a tolerance (NSD).  A = the multiset {D_T(v) : v in
+ * border(P)} (n_P values), B = {D_P(v) : v in border(T)} (n_T values), A+B their multiset union.  Percentile q of a multiset
+ * of m >= 1 values x[0] <= ... <= x[m-1]: pos = (m - 1) * q / 100.0 left to right in fp64, lo = floor(pos),
+ * hi = min(lo + 1, m - 1), value = x[lo] + (x[hi] - x[lo]) * (pos - lo) (numpy's 'linear' up to the rounding of pos; q = 100
+ * is the maximum exactly).  The entry point selects x[lo] and x[hi] exactly; the interpolation, the max of the two directions
+ * and the NSD division stay with the caller, in fp64 on the host. */
+/* workspace of aide_surface3d_scores_select: that of aide_surface3d_scores, two key lists of nvox uint64 and less than 64 KiB
+ * of counters and bins (<= aide_surface3d_ws_bytes(nvox) + 16 * nvox + 65536); 0 for nvox >= 2^31 */
+size_t aide_surface3d_select_ws_bytes(int64_t nvox);
+/* The first 17 arguments, dist and ws (of the size above) as in aide_surface3d_scores.  q[nq], tol[nt]: HOST arrays, 0 .. 4
+ * entries each, read before the call returns.  out = 52 words of 8 bytes:
+ *   [0..7]    the words of aide_surface3d_scores, the same bytes
+ *   [8 + 2*j + k]  int64: k = 0 |{a in A : a <= tol[j]}|, k = 1 the same for B; j < nt
+ *   [16 + 3*(4*s + j) + {0, 1, 2}]  set s = 0: A, 1: B, 2: A+B, percentile j < nq: int64 lo, double x[lo], double x[hi]
+ * Unused words, and the percentile words when n_P == 0 or n_T == 0, are 0.  dist is byte-equal to aide_surface3d_scores's.
+ * Launches 1-3 and 5 of aide_surface3d_scores; launch 4 also appends every distance it produces to a per-operand list of
+ * uint64 keys (the bit pattern of a non-negative double orders like the double), one integer atomic per wave and chunk, so
+ * the order of a list depends on the schedule and nothing after it does: an MSD radix select, 8 passes of 8 bits, for all
+ * targets (set, rank) at once -- per pass one launch that counts, per target, the digits of the keys that carry the target's
+ * prefix (LDS bins, integer atomics into global bins; the first pass also counts key <= bits(tol)) and one launch of a
+ * workgroup per target that picks the digit holding the rank and clears the bins.  The ranks come from out[0], out[1] and q
+ * on the device.  21 launches and two memsets whatever nq, nt and the data are; no host read, no workgroup waits for another,
+ * integer atomics only; the passes read the lists, never the volume; two calls on the same inputs give the same bytes in
+ * every word whatever the workspace held.  nq = nt = 0 gives aide_surface3d_scores's result.  AIDE_ERR_ARG before any launch
+ * for everything aide_surface3d_scores rejects, nq or nt outside 0 .. 4, a null array with a non-zero count, a q outside
+ * [0, 100] or not finite, a tol that is negative or not finite. */
+int aide_surface3d_scores_select(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2,
+                                 const void* t, int t_u8, int64_t t_s0, int64_t t_s1, int64_t t_s2,
+                                 int64_t d0, int64_t d1, int64_t d2, double sp0, double sp1, double sp2,
+                                 int cls, const double* q, int nq, const double* tol, int nt,
+                                 void* out, double* dist, void* ws, aide_stream_t stream);
 
 /* ---- the same for all cases of an epoch at once: K ragged cases concatenated as [S_total][H][W] (contiguous; what the
  * label map yields when fed all slices) with a DEVICE table slice_start[K + 1] (int64, non-decreasing, slice_start[0] >= 0,
