@@ -404,29 +404,154 @@ def case_dice_rule(sums, labelled=None, n_select=0):
     sums = np.asarray(sums, np.int64).reshape(-1, 4)
     with np.errstate(divide='ignore', invalid='ignore'):
         dice = (np.float64(2) * sums[:, 1].astype(np.float64) / (sums[:, 2] + sums[:, 3]).astype(np.float64)).astype(np.float32)
+    rank, sel = _rank_select(dice, labelled, n_select)
+    return dice, rank, sel
+
+
+def _rank_select(dice, labelled, n_select):
+    """float32 scores [K] -> (rank int32 [K]: ascending, NaN greatest, equal values by the lower index; selected uint8 [K])"""
     key = np.where(np.isnan(dice), np.float32(np.inf), dice)
     nan = np.isnan(dice).astype(np.int64)
     order = np.lexsort((np.arange(len(dice)), key, nan))          # last key first: NaN flag, value, case index
     rank = np.empty(len(dice), np.int32)
     rank[order] = np.arange(len(dice), dtype=np.int32)
     lab = np.zeros(len(dice), bool) if labelled is None else np.asarray(labelled).astype(bool)
-    return dice, rank, ((rank < int(n_select)) & ~lab).astype(np.uint8)
+    return rank, ((rank < int(n_select)) & ~lab).astype(np.uint8)
 
 
-def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None, n_select=0, keep_largest=True):
+def _palette(palette, c, what):
+    """the palette of a C-class bank as a tuple of C distinct bytes"""
+    if palette is None:
+        raise ValueError('%s: num_classes needs the palette (num_classes distinct bytes)' % what)
+    pal = tuple(int(v) for v in palette)
+    if len(pal) != c or len(set(pal)) != c or any(not 0 <= v <= 255 for v in pal):
+        raise ValueError('%s: the palette must hold %d distinct bytes, got %r' % (what, c, pal))
+    return pal
+
+
+def _byte_classes(palette, none):
+    """uint8 -> class table of a palette of distinct bytes; `none` for a byte outside it"""
+    tbl = np.full(256, none, np.int64)
+    tbl[np.asarray(palette, np.int64)] = np.arange(len(palette))
+    return tbl
+
+
+def case_class_counts(filtered, bank_plane, slice_start, palette):
+    """The host statement of `aide_case_class_counts_batched` (numpy): label maps and one bank plane, both [S_total,H,W], of K
+    concatenated cases -> int64 [K,C,3] with C = len(palette): row (k, c) = (#(f == c and b == palette[c]), #(f == c),
+    #(b == palette[c])) over the slices of case k.  A predicted value >= C (or negative) and a bank byte outside the palette
+    belong to no class."""
+    f, b = np.asarray(filtered), np.asarray(bank_plane)
+    if f.shape != b.shape:
+        raise RuntimeError('case_class_counts: shape mismatch %s vs %s' % (f.shape, b.shape))
+    c = len(palette)
+    pal = _palette(palette, c, 'case_class_counts')
+    st = _starts(slice_start, f.shape[0])
+    cb = _byte_classes(pal, c)[b.astype(np.uint8)]
+    cf = np.where((f >= 0) & (f < c), f, c).astype(np.int64)
+    out = np.zeros((len(st) - 1, c, 3), np.int64)
+    for k, (lo, hi) in enumerate(zip(st, st[1:])):
+        x, y = cf[lo:hi].reshape(-1), cb[lo:hi].reshape(-1)
+        out[k, :, 0] = np.bincount(x[x == y], minlength=c + 1)[:c]
+        out[k, :, 1] = np.bincount(x, minlength=c + 1)[:c]
+        out[k, :, 2] = np.bincount(y, minlength=c + 1)[:c]
+    return out
+
+
+def case_dice_rule_classes(counts, labelled=None, n_select=0):
+    """The host statement of `aide_label_refresh_select_classes` (numpy): int64 counts [K,C,3] = (I, P, T) per case and class
+    -> (class_dice float32 [K,C], dice float32 [K], rank int32 [K], selected uint8 [K]).  In float64 d_c = 2 I_c / (P_c + T_c)
+    (0 / 0 -> NaN); class_dice = float32(d_c) for every class, background included.  The case score is the float64 mean of
+    d_c over the FOREGROUND classes c = 1 .. C - 1 with P_c + T_c > 0 -- summed in ascending c, divided by their number,
+    rounded once to float32 -- and NaN when there is none: an organ absent from the prediction and the pseudo-label alike
+    says nothing about the case, one present in only one of them scores 0.  Ranking and selection are `case_dice_rule`'s.
+    With C = 2 the score is one term over 1.0: the binary rule, bit for bit."""
+    counts = np.asarray(counts, np.int64)
+    if counts.ndim != 3 or counts.shape[2] != 3 or not 2 <= counts.shape[1] <= 8:
+        raise RuntimeError('case_dice_rule_classes: counts [K,C,3] with C = 2 .. 8 expected, got %r' % (counts.shape,))
+    k, c = counts.shape[:2]
+    uni = counts[:, :, 1] + counts[:, :, 2]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        d = (2 * counts[:, :, 0]).astype(np.float64) / uni.astype(np.float64)
+    total, present = np.zeros(k, np.float64), np.zeros(k, np.int64)
+    for j in range(1, c):                                         # the fixed order of the device sum
+        has = uni[:, j] > 0
+        total = np.where(has, total + np.where(has, d[:, j], 0.0), total)
+        present += has
+    with np.errstate(divide='ignore', invalid='ignore'):
+        dice = (total / present.astype(np.float64)).astype(np.float32)        # no organ: 0 / 0, the NaN of the binary rule
+    rank, sel = _rank_select(dice, labelled, n_select)
+    return d.astype(np.float32), dice, rank, sel
+
+
+def _device_args(filt, slice_start, bank_plane, labelled):
+    if not (isinstance(bank_plane, torch.Tensor) and bank_plane.is_cuda and bank_plane.dtype == torch.uint8
+            and bank_plane.is_contiguous() and tuple(bank_plane.shape) == tuple(filt.shape)):
+        raise RuntimeError('evaluate_label_maps: bank_plane must be a contiguous uint8 HIP tensor shaped like the labels')
+    if labelled is not None and not (isinstance(labelled, torch.Tensor) and labelled.is_cuda
+                                     and labelled.dtype == torch.uint8 and labelled.numel() == slice_start.numel() - 1):
+        raise RuntimeError('evaluate_label_maps: labelled must be a uint8 HIP tensor [K]')
+
+
+def _evaluate_label_maps_classes(labels, slice_start, bank_plane, c, palette, labelled, n_select, keep_largest):
+    c = int(c)
+    if not 2 <= c <= 8:
+        raise ValueError('evaluate_label_maps: num_classes %d, 2 .. 8 are supported' % c)
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        if isinstance(palette, torch.Tensor):     # the bank's device table; the owner has checked its values
+            if not (palette.is_cuda and palette.dtype == torch.int32 and palette.dim() == 1 and palette.numel() == c
+                    and palette.is_contiguous()):
+                raise ValueError('evaluate_label_maps: a device palette must be a contiguous int32 HIP tensor [%d]' % c)
+            pal = palette
+        else:
+            pal = torch.tensor(_palette(palette, c, 'evaluate_label_maps'), dtype=torch.int32).pin_memory().to(
+                labels.device, non_blocking=True)
+        filt = keep_largest_batched(labels, slice_start, num_classes=c) if keep_largest else labels.to(torch.uint8).contiguous()
+        _device_args(filt, slice_start, bank_plane, labelled)
+        k = slice_start.numel() - 1
+        dev = filt.device
+        counts = torch.empty(k, c, 3, device=dev, dtype=torch.int64)
+        cd = torch.empty(k, c, device=dev, dtype=torch.float32)
+        dice = torch.empty(k, device=dev, dtype=torch.float32)
+        rank = torch.empty(k, device=dev, dtype=torch.int32)
+        sel = torch.empty(k, device=dev, dtype=torch.uint8)
+        check(lib.aide_case_class_counts_batched(ptr(filt), ptr(bank_plane), ptr(slice_start), k, *filt.shape, ptr(pal), c,
+                                                 ptr(counts), stream_ptr()), 'case_class_counts_batched')
+        check(lib.aide_label_refresh_select_classes(ptr(counts), ptr(labelled) if labelled is not None else None, k, c,
+                                                    int(n_select), ptr(cd), ptr(dice), ptr(rank), ptr(sel), stream_ptr()),
+              'label_refresh_select_classes')
+        return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
+    if isinstance(palette, torch.Tensor):
+        palette = palette.tolist()
+    pal = _palette(palette, c, 'evaluate_label_maps')
+    lab = np.asarray(labels)
+    st = _starts(slice_start, lab.shape[0])
+    filt = keep_largest_batched(lab, st, num_classes=c) if keep_largest else lab.astype(np.uint8)
+    counts = case_class_counts(filt, bank_plane, st, pal)
+    cd, dice, rank, sel = case_dice_rule_classes(counts, labelled, n_select)
+    return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
+
+
+def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None, n_select=0, keep_largest=True,
+                        num_classes=None, palette=None):
     """Label maps [S_total,H,W] of K concatenated cases against one plane of the pseudo-label bank (uint8 [S_total,H,W]):
     dict(filtered uint8 [S_total,H,W], sums int64 [K,4] = N / sum p*t / sum p / sum t with t = (bank byte == match),
     dice float32 [K], rank int32 [K], selected uint8 [K]).  On HIP tensors seven launches, all results stay on the device and
     nothing synchronises; slice_start / labelled are then device tables (int64 [K+1] / uint8 [K]).  On numpy / CPU inputs the
-    same integers through the CPU filter."""
+    same integers through the CPU filter.
+    num_classes=C (2 .. 8) with palette = C distinct bytes (ValueError otherwise; `match` is not used): the multi-organ form.
+    The filter is `keep_largest_batched(num_classes=C)` (keep_largest=False: a plain uint8 cast), the result
+    dict(filtered, counts int64 [K,C,3], class_dice float32 [K,C], dice, rank, selected) of `case_class_counts` and
+    `case_dice_rule_classes`; on HIP tensors `aide_case_class_counts_batched` and `aide_label_refresh_select_classes`, with
+    the same no-synchronisation rule (the palette may then be the int32 HIP table its owner keeps)."""
+    if num_classes is not None:
+        return _evaluate_label_maps_classes(labels, slice_start, bank_plane, num_classes, palette, labelled, n_select,
+                                            keep_largest)
+    if palette is not None:
+        raise ValueError('evaluate_label_maps: palette goes with num_classes')
     if isinstance(labels, torch.Tensor) and labels.is_cuda:
         filt = keep_largest_batched(labels, slice_start) if keep_largest else labels.to(torch.uint8).contiguous()
-        if not (isinstance(bank_plane, torch.Tensor) and bank_plane.is_cuda and bank_plane.dtype == torch.uint8
-                and bank_plane.is_contiguous() and tuple(bank_plane.shape) == tuple(filt.shape)):
-            raise RuntimeError('evaluate_label_maps: bank_plane must be a contiguous uint8 HIP tensor shaped like the labels')
-        if labelled is not None and not (isinstance(labelled, torch.Tensor) and labelled.is_cuda
-                                         and labelled.dtype == torch.uint8 and labelled.numel() == slice_start.numel() - 1):
-            raise RuntimeError('evaluate_label_maps: labelled must be a uint8 HIP tensor [K]')
+        _device_args(filt, slice_start, bank_plane, labelled)
         k = slice_start.numel() - 1
         dev = filt.device
         sums = torch.empty(k, 4, device=dev, dtype=torch.int64)
@@ -449,12 +574,15 @@ def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None
     return dict(filtered=filt, sums=sums, dice=dice, rank=rank, selected=sel)
 
 
-def evaluate_cases(net, modal_inputs, slice_start, bank_plane, match=63, batch_size=16, labelled=None, n_select=0):
+def evaluate_cases(net, modal_inputs, slice_start, bank_plane, match=63, batch_size=16, labelled=None, n_select=0,
+                   num_classes=None, palette=None):
     """All cases of an epoch in one pass: `modal_inputs` = (inphase[, outphase]), each [S_total,3,H,W] with the slices of the
     K cases concatenated.  The forward batches may cross case boundaries (eval-mode BatchNorm: slices are independent);
-    filter, sums, Dice and ranking are `evaluate_label_maps`.  Nothing leaves the device."""
+    filter, sums, Dice and ranking are `evaluate_label_maps` (num_classes / palette: its multi-organ form, for a C-class
+    network).  Nothing leaves the device."""
     labels = predict_labels(net, *modal_inputs, batch_size=batch_size)
-    return evaluate_label_maps(labels, slice_start, bank_plane, match=match, labelled=labelled, n_select=n_select)
+    return evaluate_label_maps(labels, slice_start, bank_plane, match=match, labelled=labelled, n_select=n_select,
+                               num_classes=num_classes, palette=palette)
 
 
 # ---- all IMAGES of an epoch (the epoch end of trainkidney_proposed_mask1.py:373-434 and

@@ -16,6 +16,12 @@ Ranking: ascending Dice, NaN greatest (as torch's sort), equal values by the low
 project's rule: the reference's `Tensor.sort()` is not stable, so a tie at the selection boundary has no defined winner
 there.
 
+`PseudoLabelBank(..., num_classes=C)` is the multi-organ form (the reference's scripts are liver-only, so the rule is this
+project's, `inference.case_dice_rule_classes`): class c <-> palette[c], the case score is the mean Dice of the organs present
+in the prediction or the pseudo-label, and the selected cases get `palette[prediction]` (`aide_case_class_counts_batched`,
+`aide_label_refresh_select_classes`, `aide_label_bank_update_classes`); `targets(index=True)` gathers class-index targets
+(`aide_label_bank_targets_index`).
+
 `ImageLabelBank` is the per-IMAGE form of the kidney and breast scripts (no component filter, Dice2d with union == 0 -> 0.0,
 `--update_percent`, an empty prediction is never written; `aide_image_*` of csrc/labelbank_image.hip): see its docstring."""
 import os
@@ -37,9 +43,13 @@ def refresh_gate(epoch, warmup_epoch):
 class PseudoLabelBank(object):
     """initial_masks_u8: [S_total,H,W] uint8, the slices of K cases concatenated (palette bytes, what the loader decodes from
     the mask PNG); slice_start: K + 1 ints; labelled_cases: indices of the cases whose labels are never rewritten.
-    A HIP tensor (or device=...) keeps the bank on the device; numpy / CPU input keeps a numpy bank."""
+    A HIP tensor (or device=...) keeps the bank on the device; numpy / CPU input keeps a numpy bank.
+    num_classes=C (2 .. 8, == len(palette), distinct palette bytes): the multi-organ form -- every case is scored per class
+    against the planes `bank byte == palette[c]` and rewritten with `palette[prediction]`; `case_dice()`, `modify_list`,
+    `export_png`, the gate and `n_select` keep their rules (the bank bytes are the PNG bytes either way)."""
 
-    def __init__(self, initial_masks_u8, slice_start, labelled_cases, palette=CHAOS_PALETTE, device=None, case_ids=None):
+    def __init__(self, initial_masks_u8, slice_start, labelled_cases, palette=CHAOS_PALETTE, device=None, case_ids=None,
+                 num_classes=None):
         on_dev = isinstance(initial_masks_u8, torch.Tensor) and initial_masks_u8.is_cuda
         if device is None and on_dev:
             device = initial_masks_u8.device
@@ -58,6 +68,13 @@ class PseudoLabelBank(object):
         if not 1 <= len(self.palette) <= 8:
             raise RuntimeError('PseudoLabelBank: 1 .. 8 palette values')
         self.match = self.palette[1] if len(self.palette) > 1 else self.palette[0]
+        self.num_classes = None if num_classes is None else int(num_classes)
+        if self.num_classes is not None:
+            c = self.num_classes
+            if not 2 <= c <= 8 or c != len(self.palette) or len(set(self.palette)) != c or \
+                    any(not 0 <= v <= 255 for v in self.palette):
+                raise ValueError('PseudoLabelBank: num_classes %d needs a palette of as many distinct bytes (2 .. 8), got %r'
+                                 % (c, self.palette))
         lab = np.zeros(self.K, np.uint8)
         for k in labelled_cases:
             lab[int(k)] = 1
@@ -71,6 +88,7 @@ class PseudoLabelBank(object):
             self._labelled = torch.from_numpy(lab).to(self.device)
             self._palette = torch.tensor(self.palette, dtype=torch.int32).to(self.device)
             self._dice = torch.zeros(2, self.K, device=self.device, dtype=torch.float32)
+            self._class_dice = torch.zeros(2, self.K, self.num_classes or 0, device=self.device, dtype=torch.float32)
             self.rank = torch.zeros(2, self.K, device=self.device, dtype=torch.int32)
             self.selected = torch.zeros(2, self.K, device=self.device, dtype=torch.uint8)
             self.modified = torch.zeros(2, self.K, device=self.device, dtype=torch.uint8)
@@ -78,6 +96,7 @@ class PseudoLabelBank(object):
             m = np.ascontiguousarray(m.numpy() if isinstance(m, torch.Tensor) else m)
             self.bank = np.stack([m, m])
             self._dice = np.zeros((2, self.K), np.float32)
+            self._class_dice = np.zeros((2, self.K, self.num_classes or 0), np.float32)
             self.rank = np.zeros((2, self.K), np.int32)
             self.selected = np.zeros((2, self.K), np.uint8)
             self.modified = np.zeros((2, self.K), np.uint8)
@@ -86,37 +105,56 @@ class PseudoLabelBank(object):
     def refresh_from_labels(self, labels1, labels2, epoch, warmup_epoch, keep_largest=True):
         """labels1 / labels2: the two networks' label maps [S_total,H,W] of all cases.  Case Dice and ranking are taken every
         epoch; the selected cases' planes are rewritten only while the gate of :528 is open.  -> whether it was.  On the
-        device: no host synchronisation (`selected` never leaves it)."""
+        device: no host synchronisation (`selected` never leaves it).  With num_classes the label maps carry class values
+        0 .. C - 1, the filter is the per-class one, and a selected case gets `palette[filtered]` (a value >= C, which only an
+        unfiltered map can hold, writes palette[0])."""
         from ._lib import lib, check
         from .ops import ptr, stream_ptr
         write = refresh_gate(epoch, warmup_epoch)
+        c = self.num_classes
         for n, labels in enumerate((labels1, labels2)):
             if self.device is not None:
                 if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
                     raise RuntimeError('PseudoLabelBank: the bank is on %s, the label maps must be too' % self.device)
-                r = evaluate_label_maps(labels, self._start, self.bank[n], self.match, self._labelled, self.n_select, keep_largest)
+                r = evaluate_label_maps(labels, self._start, self.bank[n], self.match, self._labelled, self.n_select, keep_largest,
+                                        num_classes=c, palette=self._palette if c else None)
                 self._dice[n].copy_(r['dice'])
                 self.rank[n].copy_(r['rank'])
                 self.selected[n].copy_(r['selected'])
+                if c:
+                    self._class_dice[n].copy_(r['class_dice'])
                 if write:
                     f = r['filtered']
-                    check(lib.aide_label_bank_update(ptr(f), ptr(r['selected']), ptr(self._start), self.K, *f.shape, LIVER,
-                                                     ptr(self.bank[n]), stream_ptr()), 'label_bank_update')
+                    if c:
+                        check(lib.aide_label_bank_update_classes(ptr(f), ptr(r['selected']), ptr(self._start), self.K, *f.shape,
+                                                                 ptr(self._palette), c, ptr(self.bank[n]), stream_ptr()),
+                              'label_bank_update_classes')
+                    else:
+                        check(lib.aide_label_bank_update(ptr(f), ptr(r['selected']), ptr(self._start), self.K, *f.shape, LIVER,
+                                                         ptr(self.bank[n]), stream_ptr()), 'label_bank_update')
                     self.modified[n].bitwise_or_(r['selected'])
             else:
                 r = evaluate_label_maps(np.asarray(labels), self.slice_start, self.bank[n], self.match, self.labelled_host,
-                                        self.n_select, keep_largest)
+                                        self.n_select, keep_largest, num_classes=c, palette=self.palette if c else None)
                 self._dice[n], self.rank[n], self.selected[n] = r['dice'], r['rank'], r['selected']
+                if c:
+                    self._class_dice[n] = r['class_dice']
+                    lut = np.full(256, self.palette[0], np.uint8)
+                    lut[:c] = self.palette
                 if write:
                     for k in np.flatnonzero(r['selected']):
                         a, b = self.slice_start[k], self.slice_start[k + 1]
-                        self.bank[n][a:b] = (r['filtered'][a:b] * LIVER).astype(np.uint8)     # :549-550
+                        if c:
+                            self.bank[n][a:b] = lut[r['filtered'][a:b]]
+                        else:
+                            self.bank[n][a:b] = (r['filtered'][a:b] * LIVER).astype(np.uint8)     # :549-550
                     self.modified[n] |= r['selected']
         return write
 
     def refresh(self, net1, net2, inputs, epoch, warmup_epoch, batch_size=16):
         """inputs = (inphase[, outphase]), each [S_total,3,H,W]: both networks (eval mode) predict every slice, then
-        `refresh_from_labels`."""
+        `refresh_from_labels`.  `predict_labels` is `label_map`, the arg-max over however many channels the network has
+        (2 .. 8), so a C-class network already yields the class maps the num_classes=C bank expects."""
         return self.refresh_from_labels(predict_labels(net1, *inputs, batch_size=batch_size),
                                         predict_labels(net2, *inputs, batch_size=batch_size), epoch, warmup_epoch)
 
@@ -124,6 +162,13 @@ class PseudoLabelBank(object):
         """float32 [2,K] on the host -- traincasedices1 / traincasedices2 of the last refresh (:488-489): ONE device-to-host copy.
         The epoch's numbers are then `d[n].sum() / float(K)` on the host as :495-496."""
         return self._dice.cpu() if self.device is not None else torch.from_numpy(self._dice.copy())
+
+    def class_dice(self):
+        """float32 [2,K,C] on the host -- the per-class Dice of the last refresh, background included (NaN where a class is
+        in neither the prediction nor the pseudo-label): ONE device-to-host copy.  Needs num_classes."""
+        if self.num_classes is None:
+            raise RuntimeError('PseudoLabelBank.class_dice: the bank was made without num_classes')
+        return self._class_dice.cpu() if self.device is not None else torch.from_numpy(self._class_dice.copy())
 
     def modify_list(self, net):
         """the cases of the reference's 'Mask [...] modify for netN' line (:552, :575): the first int(0.25 * K) cases in
@@ -134,14 +179,26 @@ class PseudoLabelBank(object):
         return [self.case_ids[int(k)] for k in order]
 
     # ---- next epoch ----
-    def targets(self, slice_idx, net):
+    def targets(self, slice_idx, net, index=False, ignore_index=255):
         """one-hot int64 [N,P,H,W] over the palette of network `net`'s (1 or 2) pseudo-labels for the slices `slice_idx`:
-        the loader's mask1 / mask2 (dataset.py:95-105), so `targets(...)[:, 1]` is the step's target."""
+        the loader's mask1 / mask2 (dataset.py:95-105), so `targets(...)[:, 1]` is the step's target.
+        index=True: int64 [N,H,W] class indices instead, the target form the fused multi-class losses take directly (8 bytes
+        per pixel, not 8 * P): the position of every byte in the palette, `ignore_index` for a byte outside it, and a plane of
+        `ignore_index` for a slice index outside the bank.  Needs 2 .. 8 distinct palette bytes."""
         if net not in (1, 2):
             raise ValueError('net must be 1 or 2')
         plane = self.bank[net - 1]
+        if index and not (2 <= len(self.palette) <= 8 and len(set(self.palette)) == len(self.palette)):
+            raise ValueError('PseudoLabelBank.targets(index=True): 2 .. 8 distinct palette bytes, got %r' % (self.palette,))
         if self.device is None:
             idx = np.asarray(slice_idx, np.int64).reshape(-1)
+            if index:
+                tbl = np.full(256, int(ignore_index), np.int64)
+                tbl[list(self.palette)] = np.arange(len(self.palette))
+                ok = (idx >= 0) & (idx < plane.shape[0])
+                out = tbl[plane[np.where(ok, idx, 0)]] if plane.shape[0] else np.empty((len(idx),) + plane.shape[1:], np.int64)
+                out[~ok] = int(ignore_index)
+                return torch.from_numpy(out)
             sl = plane[idx]
             return torch.from_numpy(np.stack([(sl == p) for p in self.palette], axis=1).astype(np.int64))
         from ._lib import lib, check
@@ -150,6 +207,12 @@ class PseudoLabelBank(object):
         if not idx.is_cuda:
             idx = idx.pin_memory().to(self.device, non_blocking=True)
         _, h, w = plane.shape
+        if index:
+            out = torch.empty(idx.numel(), h, w, device=self.device, dtype=torch.int64)
+            check(lib.aide_label_bank_targets_index(ptr(plane), *plane.shape, ptr(idx), idx.numel(), ptr(self._palette),
+                                                    len(self.palette), int(ignore_index), ptr(out), stream_ptr()),
+                  'label_bank_targets_index')
+            return out
         out = torch.empty(idx.numel(), len(self.palette), h, w, device=self.device, dtype=torch.int64)
         check(lib.aide_label_bank_targets(ptr(plane), *plane.shape, ptr(idx), idx.numel(), ptr(self._palette),
                                           len(self.palette), ptr(out), stream_ptr()), 'label_bank_targets')

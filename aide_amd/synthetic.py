@@ -101,3 +101,51 @@ def chaos_cases(n_cases, size=256, seed=1234, slices=(3, 7), labelled=(0,), sing
     return dict(inphase=torch.stack(a), outphase=None if single_modal else torch.stack(b),
                 truth=torch.from_numpy(np.stack(truth)), initial=torch.from_numpy(np.stack(initial)),
                 slice_start=start, labelled=[k for k in labelled if k < n_cases])
+
+
+def chaos_cases_multiorgan(n_cases, num_classes=5, size=256, seed=1234, slices=(3, 7), labelled=(0,)):
+    """`chaos_cases` for multi-organ masks: the same dict, with truth / initial carrying the bytes CHAOS_PALETTE[:num_classes]
+    (num_classes = 2 .. 5).  Organ c = 1 .. num_classes - 1 is an ellipsoid around its own point of a ring about the body
+    centre, so the organs of a case are disjoint blobs through its slices (a pixel takes the first organ that covers it);
+    every case but the first lacks each organ with probability 0.25 (some cases lack an organ altogether, and the first case
+    has them all).  initial: the truth for the labelled cases; for the others the truth shifted by a few pixels with some
+    slices emptied, and sometimes one organ missing from the pseudo-label."""
+    from .labelbank import CHAOS_PALETTE      # background, liver, right / left kidney, spleen
+    if not 2 <= num_classes <= len(CHAOS_PALETTE):
+        raise ValueError('chaos_cases_multiorgan: num_classes 2 .. %d, got %r' % (len(CHAOS_PALETTE), num_classes))
+    rng = np.random.RandomState(seed)
+    organs = num_classes - 1
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float64)
+    ring = 0.22 * size
+    # neighbours on the ring are 2 * ring * sin(pi / organs) apart and the blobs are 1.2 times as wide as high: a longer
+    # half-axis below half of that distance cannot meet its neighbour's
+    rmax = min(0.16 * size, 0.45 / 1.2 * 2 * ring * np.sin(np.pi / organs) if organs > 1 else 0.16 * size)
+    a, b, truth, initial, start = [], [], [], [], [0]
+    for k in range(n_cases):
+        ns = int(rng.randint(slices[0], slices[1] + 1))
+        dy, dx = (int(v) for v in rng.randint(-max(1, size // 16), max(1, size // 16) + 1, 2))
+        present = (rng.rand(organs) >= 0.25) | (k == 0)
+        forgotten = int(rng.randint(0, organs)) if rng.rand() < 0.3 else -1        # an organ the pseudo-label misses
+        radius = rmax * rng.uniform(0.6, 1.0, organs)
+        phase = rng.uniform(0, 2 * np.pi)
+        for s in range(ns):
+            g1, g2, _ = chaos_slice(rng, size)
+            a.append(_to_tensor_norm(g1))
+            b.append(_to_tensor_norm(g2))
+            m = np.zeros((size, size), np.uint8)
+            z = (s + 0.5) / ns * 2 - 1                                               # -1 .. 1 through the case
+            for c in range(organs):
+                r2 = radius[c] ** 2 * (1 - 0.8 * z * z)                             # the ellipsoid's section in this slice
+                ang = phase + 2 * np.pi * c / organs
+                cy, cx = size * 0.5 + ring * np.sin(ang), size * 0.5 + ring * np.cos(ang)
+                if present[c]:
+                    m[(m == 0) & ((yy - cy) ** 2 + ((xx - cx) / 1.2) ** 2 <= r2)] = CHAOS_PALETTE[c + 1]
+            truth.append(m)
+            noisy = np.roll(m, (dy, dx), (0, 1)) if rng.rand() >= 0.2 else np.zeros_like(m)
+            if forgotten >= 0:
+                noisy = np.where(noisy == CHAOS_PALETTE[forgotten + 1], 0, noisy).astype(np.uint8)
+            initial.append(m if k in labelled else noisy)
+        start.append(start[-1] + ns)
+    return dict(inphase=torch.stack(a), outphase=torch.stack(b),
+                truth=torch.from_numpy(np.stack(truth)), initial=torch.from_numpy(np.stack(initial)),
+                slice_start=start, labelled=[k for k in labelled if k < n_cases])

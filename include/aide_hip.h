@@ -676,6 +676,32 @@ int aide_label_bank_update(const unsigned char* pred, const unsigned char* selec
 int aide_label_bank_targets(const unsigned char* bank_plane, int64_t S_total, int64_t H, int64_t W, const long long* slice_idx,
                             int64_t N, const int* palette, int npal, long long* out, aide_stream_t stream);
 
+/* ---- the same for multi-organ banks: C = 2 .. 8 classes, class c <-> bank byte palette[c] (C distinct device ints in
+ * 0 .. 255; CHAOS: 0, 63, 126, 189, 252).  The reference refreshes the liver only; the rule below is this library's. */
+/* out[K][C][3] (int64) = per case and class (#(pred == c && bank == palette[c]), #(pred == c), #(bank == palette[c])) over the
+ * case's slices.  A predicted value >= C and a bank byte outside the palette belong to no class.  Integer atomics only: the
+ * same bytes from call to call.  Limits as aide_case_confusion_batched.  One memset and one launch for any K and C. */
+int aide_case_class_counts_batched(const unsigned char* pred, const unsigned char* bank_plane, const long long* slice_start,
+                                   int64_t K, int64_t S_total, int64_t H, int64_t W, const int* palette, int C, long long* out,
+                                   aide_stream_t stream);
+/* counts = aide_case_class_counts_batched's out.  class_dice[k][c] = float32(2 I / (P + T)) for every c, the division in fp64
+ * (0 / 0 -> NaN).  dice[k] = float32 of the fp64 mean of those fp64 quotients over the foreground classes c = 1 .. C - 1 with
+ * P + T > 0, summed in ascending c and divided by their number; NaN when there is none.  An organ absent from prediction and
+ * pseudo-label alike is left out, one present in only one of them scores 0.  With C = 2 the bits of aide_label_refresh_select.
+ * rank, selected, labelled, the K <= 4096 limit and the single workgroup are that function's. */
+int aide_label_refresh_select_classes(const long long* counts, const unsigned char* labelled, int64_t K, int C, int64_t n_select,
+                                      float* class_dice, float* dice, int* rank, unsigned char* selected, aide_stream_t stream);
+/* bank_plane[slices of k] = palette[pred] for every case with selected[k] != 0, read on the device; a predicted value >= C
+ * writes palette[0].  Other cases are not touched.  One launch. */
+int aide_label_bank_update_classes(const unsigned char* pred, const unsigned char* selected, const long long* slice_start,
+                                   int64_t K, int64_t S_total, int64_t H, int64_t W, const int* palette, int C,
+                                   unsigned char* bank_plane, aide_stream_t stream);
+/* out[N][H][W] (int64) = the class index of every byte of bank_plane[slice_idx[n]]: the index targets the fused losses take.
+ * A byte outside the palette gives ignore_index, a slice index outside [0, S_total) a plane of it.  N <= 65535.  One launch. */
+int aide_label_bank_targets_index(const unsigned char* bank_plane, int64_t S_total, int64_t H, int64_t W,
+                                  const long long* slice_idx, int64_t N, const int* palette, int C, int64_t ignore_index,
+                                  long long* out, aide_stream_t stream);
+
 /* ---- per-image pseudo-label bank: the label self-correction of trainkidney_proposed_mask{1,2,3}.py:373-434 and
  * trainbreast_dataset3_proposed_272cases25labeled.py:373-438.  Every training IMAGE k of K <= 2^20 is scored with Dice2d
  * (:131-141) and the worst int(update_percent * K) are rewritten.  Planes are [K][H][W] uint8, H * W < 2^31. */
