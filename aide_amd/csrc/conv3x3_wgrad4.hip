@@ -53,7 +53,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad4_kernel(const G4Args g) 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, j = lane & 31;
     const int ph = wid & 1, cb = wid >> 1;                 // position half, co block of the MFMA role
     const int hs = wid >> 1, vt_hi = wid & 1;              // input-transform role: row half, tile pair
 
@@ -265,6 +264,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad4_kernel(const G4Args g) 
     float* const raw1 = raw0 + G4_RAW;
 
     auto run = [&](auto HS) {
+    // The fragment addresses of the main loop come from a lane id of this instantiation's own (v_mbcnt behind an asm that names
+    // the half): derived from the kernel's `half` / `j` they are identical in both instantiations, hipcc keeps ONE copy above
+    // the branch, and because the region is structurised (first half, flow block, second half) the second half's copy of `j`
+    // stayed live across the first half's main loop -- in the private segment.
+    int rl;
+    asm volatile("; lane id, transform half %1\n\tv_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0"
+                 : "=v"(rl) : "n"(decltype(HS)::value));
+    const int half = rl >> 5, j = rl & 31;
     f32x16 acc[18];
 #pragma unroll
     for (int p = 0; p < 18; ++p)
@@ -352,7 +359,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad4_kernel(const G4Args g) 
     //   T[i][b] = sum_c M[i][c] G[c][b];   dWp[a][b] = sum_i G[i][a] T[i][b]
     float* xbuf = lds;
     float* slab = g.slabs + (long)split * 9 * g.Co * g.Ci;
-    const int ci = ci0 + j;
+    // the lane id is taken afresh (v_mbcnt: two VALU): `lane` / `half` / `j` carried from the kernel's head across the main
+    // loop were spilled to the private segment and reloaded around the stores of every row
+    const int el = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int ci = ci0 + (el & 31);
+    const int cw = co0 + cb * 32;                          // first co of this wave (scalar; Co % 32 == 0: all 32 rows in or out)
     auto epilogue = [&](auto PH) {
         constexpr int kph = decltype(PH)::value;
         auto partial = [&](int r, float* wp) {
@@ -386,7 +397,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad4_kernel(const G4Args g) 
             float wp[9];
             partial(rr + 8 * (1 - kph), wp);               // the partner's rows
 #pragma unroll
-            for (int o = 0; o < 9; ++o) xbuf[((wid * 72) + rr * 9 + o) * 64 + lane] = wp[o];
+            for (int o = 0; o < 9; ++o) xbuf[((wid * 72) + rr * 9 + o) * 64 + el] = wp[o];
         }
         __syncthreads();
 #pragma unroll
@@ -394,10 +405,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad4_kernel(const G4Args g) 
             const int r = rr + 8 * kph;
             float wp[9];
             partial(r, wp);
-            const int co = co0 + cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int co = cw + (r & 3) + 8 * (r >> 2) + 4 * (el >> 5);
 #pragma unroll
             for (int o = 0; o < 9; ++o)
-                if (co < g.Co) slab[((long)o * g.Co + co) * g.Ci + ci] = wp[o] + xbuf[(((wid ^ 1) * 72) + rr * 9 + o) * 64 + lane];
+                if (cw < g.Co) slab[((long)o * g.Co + co) * g.Ci + ci] = wp[o] + xbuf[(((wid ^ 1) * 72) + rr * 9 + o) * 64 + el];
         }
     };
     if (ph == 0) epilogue(ic<0>{}); else epilogue(ic<1>{});

@@ -29,6 +29,14 @@ namespace {
 
 template <int V> using ic = std::integral_constant<int, V>;
 
+// buffer stores with a 32-bit per-lane byte offset + scalar offset (the loads: common.h); voff = BUF_OOB drops the lane's store
+__device__ __forceinline__ void buf_store_f32x4(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
+}
+__device__ __forceinline__ void buf_store_f32x2(f32x2 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
+}
+
 struct W4Args {
     const float* x;
     const float* u;      // [Cin/4][18][2][Cout][2][2]  (stage, position pair, channel pair, co, position of the pair, channel of the pair)
@@ -104,10 +112,9 @@ __device__ __forceinline__ float half_total_dpp(float v) {
 template <int MODE, bool AFF = false, bool BNIN = false>
 __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform (scalar) roles
-    const int half = lane >> 5, j = lane & 31;
+    const int wid = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // wave-uniform (scalar) roles
     const int ph = wid & 1, cb = wid >> 1;                 // position half (transform rows 3ph..3ph+2), co block
+    const int hs = wid >> 1;                               // half of the input transform this wave computes
 
     // xcd_remap gives every XCD a contiguous range of logical blocks.  Their order: [pixel-tile group][split][co group]
     // [co in group][pixel tile in group] -- gp pixel tiles that stream the SAME filter slice (co tile, channel range) and gc
@@ -143,6 +150,33 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     const int s_begin = split * sps;
     const int s_end = min(s_begin + sps, a.stages_total);
 
+    const __amdgpu_buffer_rsrc_t xrs =
+        make_rsrc(a.x + (long)(pair ? 2 * n : n) * a.x_bs + (long)h0 * a.W + w0 - (a.W + 1));
+    // Filter fragments go global -> registers, never through LDS: wave (cb, ph) is the only consumer of
+    // U[p in its half][co in its block], and the packed layout [stage][p][pair][Co][2] makes one position a
+    // contiguous 512-byte dwordx2 load in exactly the MFMA A-operand lane order (lane = pair * 32 + co).
+    // (Cout % 64 == 32: the upper co block of the last workgroup reads past its rows - into the next run, or past the
+    // tensor, where the exact-size descriptor returns zeros; those accumulator rows are never stored)
+    // packed layout [stage][position pair q (18)][channel pair][Co][p & 1][2]: one dwordx4 per lane carries the A
+    // operands of BOTH K slots of two adjacent positions -- 9 filter loads per stage instead of 18 (vector-memory issue
+    // slots are the scarce resource beside the MFMAs: the ablation without any fetch ran 12-14 % faster)
+    const long ubase = ((long)9 * ph * 2 * a.Cout + co0 + cb * 32) * 4;
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.u + ubase), 0, (int)(((long)a.Cin * 36 * a.Cout - ubase) * 4), 0x00020000);
+    const unsigned upos = (unsigned)a.Cout * 32u;          // bytes per position pair
+    const unsigned upos18 = 18u * upos;                    // bytes per stage
+    // The transform half is wave-uniform.  Everything per-lane is instantiated once per half and selected by ONE branch: a
+    // branch inside the stage makes hipcc drain vmcnt to 0 at the join, i.e. wait for the filter fragments it has just
+    // requested.  Each instantiation derives every per-lane value from a lane id of its own (v_mbcnt behind an asm that
+    // names the half): were the two prologues identical, hipcc would hoist them above the branch, and because the region is
+    // structurised (first half, flow block, second half) whatever the second half needs would then stay live across the
+    // first half's main loop -- which has no register to spare: those values went to the private segment.
+    auto run = [&](auto HS) {
+    int lane;
+    asm volatile("; lane id, transform half %1\n\tv_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0"
+                 : "=v"(lane) : "n"(decltype(HS)::value));
+    const int tid = wid * 64 + lane;
+    const int half = lane >> 5, j = lane & 31;
     // ---- staging descriptors (stage-invariant) ----
     // raw interior: 4 ci x 18 rows x 8 float4 = 576 units (3 rounds, spare lanes repeat an earlier unit; canvas: 4 x 22 x 5 =
     // 440); raw edges: 4 x 18 x 2 dwords = 144 units (1 round; canvas 176); U: 2304 float4 (9 rounds)
@@ -173,27 +207,18 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
         // zeroed once in the prologue)
         ldsC = (unsigned)(c * F4_RCS + r * RRS + (pair ? (side ? 21 : 20) : (side ? 4 + TPW : 3)));
     }
-    const __amdgpu_buffer_rsrc_t xrs =
-        make_rsrc(a.x + (long)(pair ? 2 * n : n) * a.x_bs + (long)h0 * a.W + w0 - (a.W + 1));
-    // Filter fragments go global -> registers, never through LDS: wave (cb, ph) is the only consumer of
-    // U[p in its half][co in its block], and the packed layout [stage][p][pair][Co][2] makes one position a
-    // contiguous 512-byte dwordx2 load in exactly the MFMA A-operand lane order (lane = pair * 32 + co).
-    // (Cout % 64 == 32: the upper co block of the last workgroup reads past its rows - into the next run, or past the
-    // tensor, where the exact-size descriptor returns zeros; those accumulator rows are never stored)
-    // packed layout [stage][position pair q (18)][channel pair][Co][p & 1][2]: one dwordx4 per lane carries the A
-    // operands of BOTH K slots of two adjacent positions -- 9 filter loads per stage instead of 18 (vector-memory issue
-    // slots are the scarce resource beside the MFMAs: the ablation without any fetch ran 12-14 % faster)
-    const long ubase = ((long)9 * ph * 2 * a.Cout + co0 + cb * 32) * 4;
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.u + ubase), 0, (int)(((long)a.Cin * 36 * a.Cout - ubase) * 4), 0x00020000);
+    // one live register per descriptor: left transparent, hipcc carries the three addends of every LDS index into both
+    // transform-half instantiations below and adds them there -- 10 registers for 4 values, spilled around the first half
+#pragma unroll
+    for (int e = 0; e < 3; ++e) asm volatile("" : "+v"(ldsB[e]), "+v"(offB[e]));
+    asm volatile("" : "+v"(ldsC), "+v"(offC));
     const unsigned uoff = (unsigned)(half * a.Cout + j) * 16u;
-    const unsigned upos = (unsigned)a.Cout * 32u;          // bytes per position pair
 
     f32x4 rb[3];
     float rc;
     f32x4 ua[2][9];                                        // A fragments of the current / next stage: [q] = {p0k0, p0k1, p1k0, p1k1}
     auto fetch_u = [&](int q, int stage, f32x4* dst) {
-        const unsigned us = ((unsigned)min(stage, s_end - 1) * 18u + (unsigned)q) * upos;
+        const unsigned us = (unsigned)min(stage, s_end - 1) * upos18 + (unsigned)q * upos;
         dst[q] = buf_load_f32x4(urs, uoff, us);
     };
     auto fetch = [&](int l, int stage) {                   // 4 raw loads
@@ -231,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     }
 
     // ---- input transform: thread = (half hs, ci, tile) ----
-    const int item = tid & 127, hs = wid >> 1;             // hs is wave-uniform
+    const int item = tid & 127;
     // tile slot -> (tile row, tile column) of the workgroup tile; the 7 spare slots of the canvas repeat its last tile
     const int tslot = canv ? min(item >> 2, 24) : (item >> 2);
     const int trow = canv ? tslot / 5 : tslot >> 3, tcol = canv ? tslot - 5 * trow : tslot & 7;
@@ -278,10 +303,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
             tq[3 * i] = o12; tq[3 * i + 1] = o34; tq[3 * i + 2] = o05;
         }
     };
-    // The transform half is wave-uniform.  Everything from here on is instantiated once per half and
-    // selected by ONE branch: a branch inside the stage makes hipcc drain vmcnt to 0 at the join, i.e.
-    // wait for the filter fragments it has just requested.
-    auto run = [&](auto HS) {
     auto xf_math = [&]() { xf_half(HS); };
     // V[q = p / 2][channel pair][tile][e = channel of the pair][p & 1]: a thread stores the two positions of a pair as ONE
     // 8-byte store (9 per stage instead of 18) and a lane's 16-byte fragment read carries both K slots of both positions
@@ -293,10 +314,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     };
 
     f32x16 acc[18];
-#pragma unroll
-    for (int p = 0; p < 18; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][r] = 0.0f;
     f32x4 fb[3];                                           // B fragments of a position pair, requested 8 slots ahead
 
     float* const set0 = lds;
@@ -310,6 +327,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     for (int l = 0; l < 4; ++l) fetch(l, s_begin);
 #pragma unroll
     for (int q = 0; q < 9; ++q) fetch_u(q, s_begin, ua[0]);
+    // The accumulators are zeroed HERE, in the shadow of the 13 loads just issued (nothing below can start before the raw
+    // tile arrives).  Spelled as instructions and fenced: as plain assignments hipcc sank 200 of the 256 writes behind the
+    // prologue's last vector-memory wait, directly in front of the barrier that opens the main loop.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < 18; ++p) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float z;
+            if (p < F4_NAGPR) asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z));
+            else asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+            acc[p][r] = z;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
     if (pair) {                                            // the outer halo columns (-1 of A, 16 of B) of both sets, once
         for (int q = tid; q < 2 * 4 * 18 * 2; q += 256) {
             const int set = q / 144, rem = q - set * 144, c = rem / 36, rr = (rem % 36) >> 1, side = rem & 1;
@@ -387,10 +419,37 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
     // The wave with ph = 0 finishes accumulator rows r < 8, its partner r >= 8; the other half of the
     // partials travels through LDS ([wave][128][64 lanes]).
     float* xbuf = lds;
-    float* yn = a.y + (long)split * a.split_stride + (long)(pair ? 2 * n + ((j & 7) >> 2) : n) * a.y_bs;
+    // Lane-derived values of the epilogue are recomputed HERE from the lane id (v_mbcnt: two VALU): carried from the kernel's
+    // head they were live across the main loop, which has no register to spare -- hipcc spilled them to the private segment
+    // and every output row started with a scratch reload behind s_waitcnt vmcnt(0), i.e. behind the stores of the row before.
+    const int el = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int eh = el >> 5, ej = el & 31;
+    // Outputs, bias / scale and statistics go through buffer descriptors built once per wave: 32-bit per-lane offsets plus a
+    // scalar row offset instead of a 64-bit address per store, and every guard is a range check -- a lane outside the plane
+    // carries BUF_OOB (its stores are dropped, its loads read 0), and a wave whose 32 co lie past Cout (Cout % 64 == 32) gets
+    // descriptors of zero length (the range check may not see the scalar offset: tools/ubench/buf_range).  No exec-masked
+    // branch and no select around any of the memory instructions below.
+    // (ez = 0, opaque to hipcc: the descriptors are built here, behind the main loop, not ahead of it where their twelve
+    // SGPRs would be live across it)
+    int ez;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(ez));
+    const int cw = co0 + cb * 32 + ez;                     // first co of this wave (scalar)
+    const bool wlive = cw < a.Cout;                        // Cout % 32 == 0: all 32 co of a wave are in or out
     const bool add_bias = (a.bias != nullptr) && (split == 0);
-    const int oh = h0 + 4 * (canv ? j / 5 : j >> 3), ow = pair ? 4 * (j & 3) : w0 + 4 * (canv ? j % 5 : j & 7);
-    const bool pok = (!canv || j < 25) && oh < a.H && ow < a.W;   // H, W multiples of 4: a tile is in or out
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
+        a.y + (long)split * a.split_stride + (long)(pair ? 2 * n : n) * a.y_bs + ez, 0, wlive ? (int)BUF_OOB : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.bias) + ez, 0, (add_bias && wlive) ? a.Cout * 4 : 0, 0x00020000);
+    const int oh = h0 + 4 * (canv ? ej / 5 : ej >> 3), ow = pair ? 4 * (ej & 3) : w0 + 4 * (canv ? ej % 5 : ej & 7);
+    const bool pok = (!canv || ej < 25) && oh < a.H && ow < a.W;   // H, W multiples of 4: a tile is in or out
+    // byte offset of this lane's 4 x 4 output tile in row (r & 3) + 8 (r >> 2) of the wave's co block (host: < 2 GiB)
+    const unsigned yoff = pok ? ((pair ? (unsigned)((ej & 7) >> 2) * (unsigned)a.y_bs : 0u) +
+                                 (unsigned)(4 * eh * HW + oh * a.W + ow)) * 4u : BUF_OOB;
+    const unsigned boff = (unsigned)eh * 16u;              // bias / scale: co = cw + (r & 3) + 8 (r >> 2) + 4 half
+    const int nparts = a.N * a.blocks_h * a.blocks_w;
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
+        a.stats + ez, 0, (a.stats != nullptr && wlive) ? a.Cout * nparts * 8 : 0, 0x00020000);
+    const unsigned soff = ej == 31 ? (unsigned)(4 * eh * nparts + (n * a.blocks_h + th) * a.blocks_w + tw) * 8u : BUF_OOB;
     auto epilogue = [&](auto PH) {
         constexpr int kph = decltype(PH)::value;
         // two accumulator rows (r, r + 1: adjacent registers) per pass as f32x2: the output transform is ~800 scalar VALU
@@ -427,39 +486,38 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
             f32x2 yp[16];
             partial(2 * rp + 8 * (1 - kph), yp);           // the partner's rows
 #pragma unroll
-            for (int o = 0; o < 16; ++o) xbuf2[((wid * 64) + rp * 16 + o) * 64 + lane] = yp[o];
+            for (int o = 0; o < 16; ++o) xbuf2[((wid * 64) + rp * 16 + o) * 64 + el] = yp[o];
         }
-        __syncthreads();
-        // The eight bias values of this lane's output rows are fetched up front.  (Read next to their use they were eight
-        // dependent global_load -> s_waitcnt vmcnt(0) round trips per wave, each of which also waited for the output stores
-        // issued before it to be acknowledged -- stores count in vmcnt on gfx9: most of the "3.5 us of output stores" of
-        // HISTORY §4.8.)
-        float bvs[8];
+        // The eight bias (and AFF scale) values of this lane's output rows: eight buffer loads back to back, issued before the
+        // exchange barrier and waited for once.  co >= Cout and "no bias" are the descriptor's range check (reads 0).  (As
+        // guarded `a.bias[co]` reads hipcc made each one a block of its own -- scratch reload, s_waitcnt vmcnt(0), exec-masked
+        // branch, global_load_dword: eight dependent round trips behind the barrier.  Read next to their use they also waited
+        // for the output stores issued before them: stores count in vmcnt on gfx9 -- HISTORY §4.8.)
+        float bvs[8], svs[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int r = q + 8 * kph;
-            const int co = co0 + cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            bvs[q] = (add_bias && co < a.Cout) ? a.bias[co] : 0.f;
+            bvs[q] = buf_load_f32(brs, boff, (unsigned)(cw + (r & 3) + 8 * (r >> 2)) * 4u);
         }
-        float svs[8];
-        if constexpr (AFF) {
+        if constexpr (AFF) {                                 // (rows past Cout read scale 0: they are never stored)
+            const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.scale), 0, wlive ? a.Cout * 4 : 0, 0x00020000);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int r = q + 8 * kph;
-                const int co = co0 + cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                svs[q] = co < a.Cout ? a.scale[co] : 1.f;
+                svs[q] = buf_load_f32(ars, boff, (unsigned)(cw + (r & 3) + 8 * (r >> 2)) * 4u);
             }
         }
+        __syncthreads();
 #pragma unroll
         for (int rp = 0; rp < 4; ++rp) {
             f32x2 yp[16];
             partial(2 * rp + 8 * kph, yp);
 #pragma unroll
-            for (int o = 0; o < 16; ++o) yp[o] += xbuf2[(((wid ^ 1) * 64) + rp * 16 + o) * 64 + lane];
+            for (int o = 0; o < 16; ++o) yp[o] += xbuf2[(((wid ^ 1) * 64) + rp * 16 + o) * 64 + el];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int r = 2 * rp + e + 8 * kph;
-                const int co = co0 + cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const unsigned crow = (unsigned)(cw + (r & 3) + 8 * (r >> 2));     // scalar: co of lane half 0
                 if (a.stats) {                                   // wave-uniform
                     float s1 = 0.f, s2 = 0.f;
                     if (pok) {
@@ -472,39 +530,34 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_kernel(const W4Args a) {
                     // each behind its own s_waitcnt lgkmcnt(0): 80 LDS round trips per workgroup epilogue.)
                     s1 = half_total_dpp(s1);
                     s2 = half_total_dpp(s2);
-                    if (j == 31 && co < a.Cout) {
-                        const int nparts = a.N * a.blocks_h * a.blocks_w, blk = (n * a.blocks_h + th) * a.blocks_w + tw;
-                        *reinterpret_cast<f32x2*>(a.stats + ((long)co * nparts + blk) * 2) = f32x2{s1, s2};
-                    }
+                    buf_store_f32x2(f32x2{s1, s2}, srs, soff, crow * (unsigned)nparts * 8u);   // lanes j != 31: dropped
                 }
-                if (pok && co < a.Cout) {
-                    const float bv = bvs[2 * rp + e];
-                    f32x4* const p0 = reinterpret_cast<f32x4*>(yn + (long)co * HW + (long)oh * a.W + ow);
-                    f32x4 o[4];
+                const float bv = bvs[2 * rp + e];
+                const unsigned srow = crow * (unsigned)HW * 4u;
+                f32x4 o[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        o[i] = f32x4{yp[4 * i][e] + bv, yp[4 * i + 1][e] + bv, yp[4 * i + 2][e] + bv, yp[4 * i + 3][e] + bv};
-                    if constexpr (AFF) {                         // (never with accumulate / split-K: the launcher refuses)
-                        const float sv = svs[2 * rp + e];
+                for (int i = 0; i < 4; ++i)
+                    o[i] = f32x4{yp[4 * i][e] + bv, yp[4 * i + 1][e] + bv, yp[4 * i + 2][e] + bv, yp[4 * i + 3][e] + bv};
+                if constexpr (AFF) {                             // (never with accumulate / split-K: the launcher refuses)
+                    const float sv = svs[2 * rp + e];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
+                    for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const float v = __builtin_fmaf(yp[4 * i + k][e], sv, bv);
-                                o[i][k] = a.relu ? fmaxf(v, 0.f) : v;
-                            }
+                        for (int k = 0; k < 4; ++k) {
+                            const float v = __builtin_fmaf(yp[4 * i + k][e], sv, bv);
+                            o[i][k] = a.relu ? fmaxf(v, 0.f) : v;
                         }
                     }
-                    if (a.accumulate) {                          // (the four old rows as one batch of loads, one wait)
-                        f32x4 old[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) old[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p0) + (long)i * a.W);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) o[i] += old[i];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p0) + (long)i * a.W) = o[i];
                 }
+                if (a.accumulate) {                              // (the four old rows as one batch of loads, one wait)
+                    f32x4 old[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) old[i] = buf_load_f32x4(yrs, yoff, srow + (unsigned)(i * a.W) * 4u);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] += old[i];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) buf_store_f32x4(o[i], yrs, yoff, srow + (unsigned)(i * a.W) * 4u);
             }
         }
     };
@@ -736,6 +789,9 @@ int aide_conv3x3_wino4(const float* x, int64_t x_bs, const float* u, const float
     } else {
         a.y = y; a.y_bs = y_bs; a.split_stride = 0; a.bias = bias; a.accumulate = (accumulate == 1);
     }
+    // the epilogue addresses an image's outputs (pair tile: two images) and the statistics with 32-bit byte offsets
+    if (((a.pair ? a.y_bs : 0) + (long)Cout * H * W) * 4 >= (1L << 31)) return AIDE_ERR_ARG;
+    if (a.stats && (long)Cout * N * a.blocks_h * a.blocks_w * 8 >= (1L << 31)) return AIDE_ERR_ARG;
     const long nb = (long)a.blocks_w * a.blocks_h * (a.pair ? N / 2 : N) * a.n_co_tiles * splitk;
     {   // tile group per XCD (nb / 8 consecutive logical blocks).  Memory-side reads of a launch: the filter pack once per
         // pixel-tile GROUP, the input (1.44x with its halo) once per co GROUP:  bytes ~ |U| P / gp + 1.44 |x| C / gc.
