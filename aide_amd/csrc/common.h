@@ -69,6 +69,22 @@ __device__ __forceinline__ void st1(bf16_store_t* p, float v) { *p = (bf16_store
 // fp32 (a NaN logit gives 0).  Shared by aide_label_map and the per-image refresh epilogue, which must agree bit for bit.
 __device__ __forceinline__ int aide_label2(float z0, float z1) { return (z1 > z0 && expf(z0 - z1) < 1.0f) ? 1 : 0; }
 
+// fp32 soft-max of the C logits of a pixel (planes HW floats apart): z = the logits, p = the probabilities, lse = log sum exp.
+// Shared by the C-class losses, aide_label_map_mc and the ensemble vote, which must agree bit for bit.
+template <int C>
+__device__ __forceinline__ void soft_terms(const float* __restrict__ zp, int HW, float (&z)[C], float (&p)[C], float& lse) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { z[c] = zp[(long)c * HW]; m = fmaxf(m, z[c]); }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - m); s += p[c]; }
+    const float inv = 1.0f / s;
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] *= inv;
+    lse = m + logf(s);
+}
+
 static inline int aide_launch_status() { return (int)hipGetLastError(); }
 
 // Dynamic-LDS opt-in (hipFuncAttributeMaxDynamicSharedMemorySize) of a launcher's kernels: once per DEVICE -- the attribute

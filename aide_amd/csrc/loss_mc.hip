@@ -28,20 +28,6 @@ constexpr int MAXC = 8;
 struct ClassW { float w[MAXC]; };
 
 template <int C>
-__device__ __forceinline__ void soft_terms(const float* __restrict__ zp, int HW, float (&z)[C], float (&p)[C], float& lse) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { z[c] = zp[(long)c * HW]; m = fmaxf(m, z[c]); }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - m); s += p[c]; }
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = m + logf(s);
-}
-
-template <int C>
 __device__ __forceinline__ float pick(const float (&v)[C], int k) {   // v[k] without dynamic register indexing
     float r = v[0];
 #pragma unroll

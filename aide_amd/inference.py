@@ -16,6 +16,8 @@ import torch
 
 from ._lib import lib, check
 from .ops import ptr, stream_ptr
+from .ensemble import (VIEW_SETS, view_codes, view_apply_host, view_invert_host, view_stack, ensemble_vote,  # noqa: F401
+                       ensemble_vote_host, ensemble_logits, predict_ensemble)
 
 
 def label_map(logits):
@@ -36,10 +38,18 @@ def label_map(logits):
 
 def predict_labels(net, *modal_inputs, **kw):
     """Labels [S,H,W] (int64, on device) for S slices; `modal_inputs` = (inphase[, outphase]) each
-    [S,3,H,W].  The network must be in eval mode, as in the reference loop (:210 `net.eval()`)."""
+    [S,3,H,W].  The network must be in eval mode, as in the reference loop (:210 `net.eval()`).
+    views='flip2' / 'flip4' / 'd4' or a tuple of view codes (aide_amd/ensemble.py): test-time augmentation -- every slice is
+    predicted under each of the V views and the label is the first class of the largest mean soft-max (`ensemble_vote`);
+    `net` may then be a list / tuple of networks of one class count that vote together (member i * V + j = network i under
+    view j, at most 16 members, ValueError beyond), and a forward batch is V views of max(1, batch_size // V) slices.
+    views=None (the default) with one network: the single identity forward and `label_map`, as before."""
     batch_size = kw.pop('batch_size', 16)
+    views = kw.pop('views', None)
     if kw:
         raise TypeError('unexpected arguments %r' % sorted(kw))
+    if views is not None or isinstance(net, (list, tuple)):
+        return predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size)
     if net.training:
         raise RuntimeError('predict_labels needs net.eval(): train-mode BatchNorm at bs=1 is not what the '
                            'reference loop runs')
@@ -58,8 +68,11 @@ def predict_case(net, *modal_inputs, **kw):
     keep_largest=True: its largest connected component (:268), uint8, filtered on the device before anything leaves it.
     keep_largest='per_class' with num_classes=C: the largest component of every class 1 .. C - 1 (`keep_largest_per_class`),
     uint8 class values, for multi-organ networks.
-    numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered)."""
+    numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered).
+    views=...: the voted labels of `predict_labels(..., views=...)` (`net` may be a list of networks); probs=True then returns
+    (volume, mean probabilities [S,C,H,W]) -- the probabilities are the vote's, before any filter."""
     keep_largest = kw.pop('keep_largest', False)
+    want_probs = kw.pop('probs', False)
     num_classes = kw.pop('num_classes', None)
     as_numpy = kw.pop('numpy', True)
     per_class = isinstance(keep_largest, str)
@@ -71,14 +84,24 @@ def predict_case(net, *modal_inputs, **kw):
         num_classes = _num_classes(num_classes, 'predict_case')
     elif num_classes is not None:
         raise TypeError("predict_case: num_classes goes with keep_largest='per_class'")
-    vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
+    pr = None
+    if want_probs:
+        views = kw.pop('views', None)
+        batch_size = kw.pop('batch_size', 16)
+        if kw:
+            raise TypeError('unexpected arguments %r' % sorted(kw))
+        vol, pr = predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size, probs=True)
+        vol = vol.permute(1, 2, 0)
+    else:
+        vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
     if per_class:
         vol = keep_largest_per_class(vol, num_classes)
     elif keep_largest:
         vol = keep_largest_connected_components(vol)
     if not as_numpy:
-        return vol
-    return vol.contiguous().cpu().numpy()
+        return vol if pr is None else (vol, pr)
+    vol = vol.contiguous().cpu().numpy()
+    return vol if pr is None else (vol, pr.cpu().numpy())
 
 
 def Dice3d_fn(inputs, targets):
@@ -575,12 +598,12 @@ def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None
 
 
 def evaluate_cases(net, modal_inputs, slice_start, bank_plane, match=63, batch_size=16, labelled=None, n_select=0,
-                   num_classes=None, palette=None):
+                   num_classes=None, palette=None, views=None):
     """All cases of an epoch in one pass: `modal_inputs` = (inphase[, outphase]), each [S_total,3,H,W] with the slices of the
     K cases concatenated.  The forward batches may cross case boundaries (eval-mode BatchNorm: slices are independent);
     filter, sums, Dice and ranking are `evaluate_label_maps` (num_classes / palette: its multi-organ form, for a C-class
-    network).  Nothing leaves the device."""
-    labels = predict_labels(net, *modal_inputs, batch_size=batch_size)
+    network).  views: the test-time augmentation of `predict_labels` (None: the single forward).  Nothing leaves the device."""
+    labels = predict_labels(net, *modal_inputs, batch_size=batch_size, views=views)
     return evaluate_label_maps(labels, slice_start, bank_plane, match=match, labelled=labelled, n_select=n_select,
                                num_classes=num_classes, palette=palette)
 

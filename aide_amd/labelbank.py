@@ -151,12 +151,13 @@ class PseudoLabelBank(object):
                     self.modified[n] |= r['selected']
         return write
 
-    def refresh(self, net1, net2, inputs, epoch, warmup_epoch, batch_size=16):
+    def refresh(self, net1, net2, inputs, epoch, warmup_epoch, batch_size=16, views=None):
         """inputs = (inphase[, outphase]), each [S_total,3,H,W]: both networks (eval mode) predict every slice, then
         `refresh_from_labels`.  `predict_labels` is `label_map`, the arg-max over however many channels the network has
-        (2 .. 8), so a C-class network already yields the class maps the num_classes=C bank expects."""
-        return self.refresh_from_labels(predict_labels(net1, *inputs, batch_size=batch_size),
-                                        predict_labels(net2, *inputs, batch_size=batch_size), epoch, warmup_epoch)
+        (2 .. 8), so a C-class network already yields the class maps the num_classes=C bank expects.  views: the test-time
+        augmentation of `predict_labels` for each network (None: the single forward)."""
+        return self.refresh_from_labels(predict_labels(net1, *inputs, batch_size=batch_size, views=views),
+                                        predict_labels(net2, *inputs, batch_size=batch_size, views=views), epoch, warmup_epoch)
 
     def case_dice(self):
         """float32 [2,K] on the host -- traincasedices1 / traincasedices2 of the last refresh (:488-489): ONE device-to-host copy.

@@ -765,6 +765,25 @@ int aide_mc_counts_labels(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, i
  * classes >= C are not touched.  One fp64 division per term.  One launch. */
 int aide_mc_metrics_accumulate(const long long* counts, int64_t N, int C, int64_t HW, void* acc, aide_stream_t stream);
 
+/* ---- test-time augmentation (csrc/ensemble.hip): the eight flips and quarter turns of an image, exact permutations.
+ * View code v = r + 4 f, r = 0 .. 3, f = 0 / 1: view_v(x) = torch.rot90(torch.flip(x, [-1]) if f else x, r, (-2, -1)); its
+ * frame is [W][H] for odd r, which needs H == W.  views: HOST arrays of 1 .. 16 codes, duplicates allowed.  Both calls return
+ * AIDE_ERR_ARG before any launch for a null pointer, a code outside 0 .. 7, an odd-r code with H != W, a count outside
+ * 1 .. 16 or N * C * H * W >= 2^31; any H, W >= 1 (4-byte accesses: no alignment is asked of the pointers beyond a float's).
+ * One launch each, no atomics, no workspace: the same bytes from call to call. */
+/* y[V][N][C][.][.] (image stride y_bs floats, image v * N + n) with y[v][n] = view_views[v](x[n]), x[N][C][H][W] (image stride
+ * x_bs); every tile of x is read once for all V views. */
+int aide_view_stack(const float* x, int64_t x_bs, float* y, int64_t y_bs, const int* views /* HOST [V] */, int V,
+                    int N, int C, int H, int W, aide_stream_t stream);
+/* The soft vote of K members (C = 2 .. aide_seg_max_classes()): for output pixel (n, i, j) and member k = 0 .. K - 1 in order,
+ * the C logits at the position views[k] maps (i, j) to, their fp32 soft-max as aide_label_map_mc takes it, added to a
+ * per-class fp32 sum; probs (NULL, or [N][C][H][W] with image stride p_bs) = sum * (1 / K); labels[N][H][W] = the FIRST index
+ * of the largest sum.  One member under view 0 gives the labels of aide_label_map / aide_label_map_mc. */
+int aide_ensemble_vote(const float* const* logits /* HOST array of K device pointers, each [N][C][H][W] in its member's view frame */,
+                       const int* views /* HOST [K] */, int K, int64_t l_bs, int N, int C, int H, int W,
+                       long long* labels /* [N][H][W] */, float* probs /* NULL or [N][C][H][W] */, int64_t p_bs,
+                       aide_stream_t stream);
+
 /* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
  * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
  * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
