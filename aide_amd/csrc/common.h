@@ -165,6 +165,16 @@ template <int V0, int... Vs, class F> auto aide_pick(int v, F&& f) {
     else { if (v == V0) return f(std::integral_constant<int, V0>{}); return aide_pick<Vs...>(v, f); }
 }
 
+// Ragged batches of cases ([S_total][H][W] planes with a device table start[K + 1]): slices [s0, s0 + ns) of case k.  A table
+// entry outside [0, S_total] or below its predecessor is clamped, so that no address derived from it leaves the buffers
+__device__ __forceinline__ void case_range(const long long* start, int k, int S_total, int& s0, int& ns) {
+    long long a = start[k], b = start[k + 1];
+    a = a < 0 ? 0 : (a > S_total ? S_total : a);
+    b = b < a ? a : (b > S_total ? S_total : b);
+    s0 = (int)a;
+    ns = (int)(b - a);
+}
+
 // XCD-aware bijective remap of a 1-D block id: the hardware dispatches block b to XCD b % 8;
 // give every XCD a contiguous range of logical tiles so neighbouring tiles (shared halo rows,
 // shared filter blocks) hit the same private L2 (cdna_hip_programming.md T1).

@@ -5,40 +5,136 @@
 // (V != 0; face neighbours of EQUAL value are connected).  The root of a set is always its smallest index, so it IS the
 // component's first voxel in raster order.  Invariant: parent[i] <= i, and after the launch that initialises it every
 // global write to `parent` is an atomicMin -- parents only decrease, so every find and union loop ends, and no workgroup
-// ever waits for another (no spin, no co-residency assumption).  Launches:
-//   1 lcc_local   one workgroup per 4 x 16 x 16 tile: union-find in LDS; parent[i] = first voxel of i's blob inside the
-//                 tile (-1 for background), area[i] = that blob's voxel count at its first voxel, 0 elsewhere
-//   2 lcc_border  per tile, face-adjacent equal-valued pairs across its three lower faces joined with atomicMin; parent
-//                 words other workgroups write are read with agent-scope relaxed atomic loads (no stale L1 / L2 line)
-//   3 lcc_count   every tile-blob root that is no longer a root adds its area to its set's root (wave-aggregated atomics)
-//   4 lcc_select  key = (area << 32) | (0x7fffffff - root), block max, one atomicMax per block; flags whether any root
-//                 (hence any voxel) holds a positive value
-//   5 lcc_write   out[i] = 1 where find(i) is the chosen root (nothing when no voxel is positive: the reference's
-//                 `if mask.max() > 0`)
+// ever waits for another (no spin, no co-residency assumption).  One pipeline of five launches:
+//   1 local   one workgroup per 16 x 16 x 4 tile: union-find in LDS; parent[i] = first voxel of i's blob inside the tile
+//             (-1 for background), area[i] = that blob's voxel count at its first voxel, 0 elsewhere
+//   2 border  per tile, face-adjacent equal-valued pairs across its three lower faces joined with atomicMin; parent words
+//             other workgroups write are read with agent-scope relaxed atomic loads (no stale L1 / L2 line)
+//   3 count   every tile-blob root that is no longer a root adds its area to its set's root (wave-aggregated atomics)
+//   4 select  key = (area << 32) | (0x7fffffff - root), block max, one atomicMax per block
+//   5 write   out[i] = 1 (the voxel's class) where find(i) is the chosen root
 // Everything is integer and the result does not depend on the schedule.
 //
-// Batched form (aide_keep_largest_cc3d_batched, aide_case_confusion_batched): the label maps of K ragged cases concatenated
-// as [S_total][H][W] with a device table slice_start[K + 1].  Case k's logical volume is [H][W][S_k]; its voxel (h, w, s) is
-// node base_k + (h * W + w) * S_k + s with base_k = slice_start[k] * H * W, so a case owns a contiguous range of nodes whose
-// order is its own raster order: the same invariants, the same tie rule, and a union never leaves the range because a tile
-// never leaves its case.  Every launch has the grid (chunks of the plane, K): blockIdx.y is the case, the block walks the
-// case's slices, and the number of launches is the per-case form's five whatever K is.
+// Every stage is written once over a `View`: a strided volume with logical dims, element strides and the node index of
+// its first voxel.  Two geometries supply views and index maps, nothing else:
+//   Strided  (aide_keep_largest_cc3d[_classes]) the caller's volume itself, node base 0.  A thread of a tile walks the 4-deep
+//            logical axis 0 and the 256 threads cover (i1, i2); the grid is strided over the tiles; lanes run along i2.
+//   Ragged   (aide_keep_largest_cc3d[_classes]_batched) K cases concatenated as [S_total][H][W] with a device table
+//            slice_start[K + 1]; blockIdx.y is the case.  Case k is the view with dims (H, W, S_k), strides (W, 1, H * W),
+//            data offset and node base slice_start[k] * H * W: a case owns a contiguous range of nodes whose order is its own
+//            raster order, a union never leaves the range because a tile never leaves its case, and nodes outside the
+//            (clamped) case ranges are neither read nor written.  A thread walks the 4-deep logical axis 2 (slices), the 256
+//            threads cover a 16 x 16 patch of (h, w), and a block walks its patch (its 256 plane positions in count, select
+//            and write) through all the slices of the case; lanes run along w.
+// In both, the local index inside a tile is raster order of the logical index, so a tile-blob's lowest local index is its
+// first voxel.  The number of launches is five whatever K is.
 //
-// Per-class form (aide_keep_largest_cc3d_classes[_batched]): blobs of different values are separate sets already, so launches
-// 1 - 3 are shared as they are and only select and write differ: one key per class value 1 .. C - 1 (the value read at the
-// root), out[i] = the voxel's own class where its root is that class's winner.  The 3 C control words per volume (keys, root
-// counts, area sums) are cleared by one memset in front of launch 1: five launches and one memset whatever C and K are.
+// Modes: BINARY keeps the largest component of all values (nothing when no voxel is positive: the reference's
+// `if mask.max() > 0`); control words per case: key, positive flag -- cleared by launch 1.  CLASSES: blobs of different
+// values are separate sets already, so launches 1 - 3 are shared as they are and only select and write differ: one key per
+// class value 1 .. C - 1 (the value read at the root), out[i] = the voxel's own class where its root is that class's winner.
+// The 3 C control words per case (keys, root counts, area sums) are cleared by one memset in front of launch 1: five
+// launches and one memset whatever C and K are.
 #include "common.h"
 
 namespace {
 
-constexpr int TX = 16, TY = 16, TZ = 4, TILE = TX * TY * TZ;   // tile of logical (i0, i1, i2) = (z, y, x)
+constexpr int TQ = 16, TZ = 4, TILE = TQ * TQ * TZ;   // a tile: 16 x 16 threads, each walking TZ voxels of the slab axis
 
-struct Vol {
-    const long long* v;
-    long s0, s1, s2;   // element strides of the logical dims
+struct View {
+    const long long* v;   // voxel (0, 0, 0)
+    long s0, s1, s2;      // element strides of the logical dims
     int d0, d1, d2;
-    int tx, ty;        // tiles along i2, i1
+    int base;             // node of voxel (0, 0, 0); node of (i0, i1, i2) = base + raster index
+    __device__ __forceinline__ bool has(int i0, int i1, int i2) const { return i0 < d0 && i1 < d1 && i2 < d2; }
+    __device__ __forceinline__ long off(int i0, int i1, int i2) const { return (long)i0 * s0 + (long)i1 * s1 + (long)i2 * s2; }
+    __device__ __forceinline__ int node(int i0, int i1, int i2) const { return base + (i0 * d1 + i1) * d2 + i2; }
+};
+
+// Thread coordinates of a tile: z = 0 .. TZ - 1 along the slab axis, (p, q) = (t / 16, t % 16), q along the lanes.
+// SLAB = 0: logical (z, p, q), tile extents 4 x 16 x 16.  SLAB = 2: logical (p, q, z), extents 16 x 16 x 4.
+template <int SLAB>
+__device__ __forceinline__ void to_logical(int z, int p, int q, int& l0, int& l1, int& l2) {
+    if (SLAB == 0) { l0 = z; l1 = p; l2 = q; } else { l0 = p; l1 = q; l2 = z; }
+}
+// local index = raster order of the logical index inside the tile; the strides of logical axes 0 and 1 in it
+template <int SLAB> constexpr int LS1 = SLAB == 0 ? TQ : TZ;
+template <int SLAB> constexpr int LS0 = TQ * LS1<SLAB>;
+
+struct Strided {
+    static constexpr int SLAB = 0;
+    View g;
+    int t1, t2, tiles;    // tiles along i1 and i2, and in all
+    __device__ View view() const { return g; }
+    __device__ int tile_begin() const { return blockIdx.x; }
+    __device__ int tile_end(const View&) const { return tiles; }
+    __device__ int tile_step() const { return gridDim.x; }
+    __device__ void tile_origin(int tile, int& o0, int& o1, int& o2) const {
+        const int t12 = t1 * t2, a = tile / t12, r = tile - a * t12, b = r / t2;
+        o0 = a * TZ; o1 = b * TQ; o2 = (r - b * t2) * TQ;
+    }
+    // count: the block's run of nodes
+    __device__ void count_run(const View& g, int& first, int& count) const {
+        const int b = (int)blockIdx.x * 256;
+        first = g.base + b;
+        count = min(256, g.d0 * g.d1 * g.d2 - b);
+    }
+    // A thread's nodes in select and write: f(node, offset of its value, index in `out`).  The offset is a callable: it is
+    // decoded from the node only where it is needed.  Select is grid-strided over the nodes, write has one node per thread
+    template <class F>
+    __device__ void visit(const View& g, int i, F& f) const {
+        f(g.base + i, [&] {
+            const int plane = g.d1 * g.d2, i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2;
+            return g.off(i0, i1, r - i1 * g.d2);
+        }, (long)i);
+    }
+    template <class F>
+    __device__ void select_nodes(const View& g, F f) const {
+        const unsigned n = (unsigned)(g.d0 * g.d1 * g.d2);
+        for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < n; u += gridDim.x * 256u) visit(g, (int)u, f);
+    }
+    template <class F>
+    __device__ void write_nodes(const View& g, F f) const {
+        const unsigned u = blockIdx.x * 256u + threadIdx.x;
+        if (u < (unsigned)(g.d0 * g.d1 * g.d2)) visit(g, (int)u, f);
+    }
+};
+
+struct Ragged {
+    static constexpr int SLAB = 2;
+    const long long* v;       // [S_total][H][W], contiguous
+    const long long* start;   // [K + 1] first slice of every case (device)
+    int S_total, H, W;
+    int tw;                   // 16-wide tiles along w
+    __device__ View view() const {
+        int s0, ns;
+        case_range(start, blockIdx.y, S_total, s0, ns);
+        const long hw = (long)H * W;
+        return View{v + s0 * hw, W, 1, hw, H, W, ns, (int)(s0 * hw)};
+    }
+    // the block's 16 x 16 patch of the plane, TZ slices at a time
+    __device__ int tile_begin() const { return 0; }
+    __device__ int tile_end(const View& g) const { return (g.d2 + TZ - 1) / TZ; }
+    __device__ int tile_step() const { return 1; }
+    __device__ void tile_origin(int tile, int& o0, int& o1, int& o2) const {
+        o0 = (int)(blockIdx.x / tw) * TQ; o1 = (int)(blockIdx.x % tw) * TQ; o2 = tile * TZ;
+    }
+    // the nodes of 256 plane positions of a case are one contiguous run
+    __device__ void count_run(const View& g, int& first, int& count) const {
+        const int p0 = (int)blockIdx.x * 256;
+        first = g.base + p0 * g.d2;
+        count = min(256, g.d0 * g.d1 - p0) * g.d2;
+    }
+    // select and write: thread = one plane position p = h * W + w of the case, all its slices (consecutive nodes)
+    template <class F>
+    __device__ void select_nodes(const View& g, F f) const {
+        const long p = (long)blockIdx.x * 256 + threadIdx.x;
+        if (p >= (long)g.d0 * g.d1) return;
+        const int first = g.base + (int)p * g.d2;
+        for (int s = 0; s < g.d2; ++s) f(first + s, [&] { return s * g.s2 + p; }, g.base + s * g.s2 + p);
+    }
+    template <class F>
+    __device__ void write_nodes(const View& g, F f) const { select_nodes(g, f); }
 };
 
 __device__ __forceinline__ int ld_agent(const int* p) {
@@ -91,469 +187,132 @@ __device__ __forceinline__ void lds_unite(int* lp, int a, int b) {
     }
 }
 
-__device__ __forceinline__ void tile_origin(const Vol& g, int tile, int& z0, int& y0, int& x0) {
-    const int tyx = g.tx * g.ty;
-    const int tz = tile / tyx, r = tile - tz * tyx, ty = r / g.tx;
-    z0 = tz * TZ; y0 = ty * TY; x0 = (r - ty * g.tx) * TX;
-}
-
-// thread t owns (y, x) = (t / 16, t % 16) of the tile at z = 0 .. 3: local index e = z * 256 + t
-__global__ __launch_bounds__(256) void lcc_local_kernel(Vol g, long tiles, int* __restrict__ parent,
-                                                        int* __restrict__ area, unsigned long long* __restrict__ ctrl) {
-    __shared__ long long val[TILE];
-    __shared__ int lp[TILE];
-    __shared__ int cnt[TILE];
-    const int t = threadIdx.x, y = t >> 4, x = t & 15;
-    const int plane = g.d1 * g.d2;
-    if (blockIdx.x == 0 && t == 0) { ctrl[0] = 0ull; ctrl[1] = 0ull; }
-    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        int z0, y0, x0;
-        tile_origin(g, (int)tile, z0, y0, x0);
-        const bool in_yx = y0 + y < g.d1 && x0 + x < g.d2;
-        __syncthreads();                          // the previous tile's LDS is read to the end
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = z * 256 + t;
-            long long v = 0;
-            if (in_yx && z0 + z < g.d0) v = g.v[(long)(z0 + z) * g.s0 + (long)(y0 + y) * g.s1 + (long)(x0 + x) * g.s2];
-            val[e] = v;
-            lp[e] = v != 0 ? e : -1;
-            cnt[e] = 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = z * 256 + t;
-            const long long v = val[e];
-            if (v == 0) continue;                 // (out-of-volume voxels read as background)
-            if (x > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
-            if (y > 0 && val[e - TX] == v) lds_unite(lp, e - TX, e);
-            if (z > 0 && val[e - TX * TY] == v) lds_unite(lp, e - TX * TY, e);
-        }
-        __syncthreads();
-        int root[TZ];
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = z * 256 + t;
-            root[z] = val[e] != 0 ? lds_find(lp, e) : -1;
-            if (root[z] >= 0) atomicAdd(&cnt[root[z]], 1);
-        }
-        __syncthreads();
-        if (!in_yx) continue;
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            if (z0 + z >= g.d0) break;
-            const int e = z * 256 + t;
-            const int gi = (z0 + z) * plane + (y0 + y) * g.d2 + x0 + x;
-            int gr = -1;
-            if (root[z] >= 0) {   // local order (z, y, x) is raster order: the tile-blob's first voxel has the lowest index
-                const int r = root[z], rz = r >> 8, ry = (r >> 4) & 15, rx = r & 15;
-                gr = (z0 + rz) * plane + (y0 + ry) * g.d2 + x0 + rx;
-            }
-            parent[gi] = gr;
-            area[gi] = cnt[e];
-        }
-    }
-}
-
-// the three lower faces of a tile: x face (TZ x TY pairs), y face (TZ x TX), z face (TY x TX)
-__global__ __launch_bounds__(256) void lcc_border_kernel(Vol g, long tiles, int* __restrict__ parent) {
-    const int plane = g.d1 * g.d2;
-    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        int z0, y0, x0;
-        tile_origin(g, (int)tile, z0, y0, x0);
-        for (int k = threadIdx.x; k < TZ * TY + TZ * TX + TY * TX; k += 256) {
-            int z, y, x, dz = 0, dy = 0, dx = 0;
-            if (k < TZ * TY) {
-                if (x0 == 0) continue;
-                z = k / TY; y = k % TY; x = 0; dx = 1;
-            } else if (k < TZ * TY + TZ * TX) {
-                if (y0 == 0) continue;
-                const int j = k - TZ * TY;
-                z = j / TX; x = j % TX; y = 0; dy = 1;
-            } else {
-                if (z0 == 0) continue;
-                const int j = k - TZ * TY - TZ * TX;
-                y = j / TX; x = j % TX; z = 0; dz = 1;
-            }
-            const int a0 = z0 + z, a1 = y0 + y, a2 = x0 + x;
-            if (a0 >= g.d0 || a1 >= g.d1 || a2 >= g.d2) continue;
-            const long off = (long)a0 * g.s0 + (long)a1 * g.s1 + (long)a2 * g.s2;
-            const long long v = g.v[off];
-            if (v == 0) continue;
-            const long long w = g.v[off - dz * g.s0 - dy * g.s1 - dx * g.s2];
-            if (w != v) continue;
-            const int gi = a0 * plane + a1 * g.d2 + a2;
-            unite(parent, gi - dz * plane - dy * g.d2 - dx, gi);
-        }
-    }
-}
-
 __device__ __forceinline__ int find_plain(const int* parent, int x) {
     int q = parent[x];
     while (q != x) { x = q; q = parent[x]; }
     return x;
 }
 
-// tile-blob roots that were joined to another set add their area to its root.  Lanes of one wave that add to the same
-// root are summed first: one atomic per (wave, root)
-__global__ __launch_bounds__(256) void lcc_count_kernel(int* __restrict__ parent, int* __restrict__ area, int n) {
-    const int i = (int)min(blockIdx.x * 256u + threadIdx.x, (unsigned)n);
-    int a = 0, r = -1;
-    if (i < n) {
-        a = area[i];
-        if (a > 0) {
-            r = find_plain(parent, i);
-            if (r != i) atomicMin(parent + i, r);
-            else a = 0;
-        }
-    }
-    unsigned long long pending = __ballot(a > 0);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int rl = __shfl(r, leader);
-        const bool mine = a > 0 && r == rl;
-        int s = mine ? a : 0;
+// ---- 1 local: the tile at logical origin (o0, o1, o2); out-of-volume voxels read as background ----
+// A thread's column: TZ voxels along the slab axis from the tile's voxel (c0, c1, c2), each step LZ local indices,
+// slab_stride elements and slab_nodes nodes further on; `depth` of them lie inside the volume
+template <int SLAB>
+__device__ __forceinline__ void tile_local(const View& g, int o0, int o1, int o2, int* __restrict__ parent,
+                                           int* __restrict__ area, long long* val, int* lp, int* cnt) {
+    constexpr int L0 = LS0<SLAB>, L1 = LS1<SLAB>, LZ = SLAB == 0 ? L0 : 1;
+    const int t = threadIdx.x, p = t >> 4, q = t & 15;
+    int c0, c1, c2;
+    to_logical<SLAB>(0, p, q, c0, c1, c2);
+    const int e0 = c0 * L0 + c1 * L1 + c2;
+    const int depth = g.has(o0 + c0, o1 + c1, o2 + c2) ? (SLAB == 0 ? g.d0 - o0 : g.d2 - o2) : 0;
+    const long off0 = g.off(o0 + c0, o1 + c1, o2 + c2), slab_stride = SLAB == 0 ? g.s0 : g.s2;
+    const int node0 = depth ? g.node(o0 + c0, o1 + c1, o2 + c2) : 0, slab_nodes = SLAB == 0 ? g.d1 * g.d2 : 1;
+    __syncthreads();                              // the previous tile's LDS is read to the end
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(area + rl, s);
-        if (mine) a = 0;
-        pending &= ~__ballot(mine);
-    }
-}
-
-__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-// ctrl[0] = max key over the roots, ctrl[1] = 1 when some root (so some voxel) holds a positive value
-__global__ __launch_bounds__(256) void lcc_select_kernel(Vol g, const int* __restrict__ parent, const int* __restrict__ area,
-                                                         int n, unsigned long long* __restrict__ ctrl) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    unsigned long long key = 0;
-    int pos = 0;
-    const int plane = g.d1 * g.d2;
-    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
-        const int i = (int)u;
-        if (parent[i] != i) continue;
-        key = umax64(key, ((unsigned long long)(unsigned)area[i] << 32) | (unsigned)(0x7fffffff - i));
-        if (!pos) {
-            const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
-            pos = g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2] > 0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        key = umax64(key, __shfl_xor(key, o));
-        pos |= __shfl_xor(pos, o);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { sk[wid] = key; sp[wid] = pos; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        key = umax64(umax64(sk[0], sk[1]), umax64(sk[2], sk[3]));
-        pos = sp[0] | sp[1] | sp[2] | sp[3];
-        if (key) atomicMax(ctrl, key);
-        if (pos) atomicMax(ctrl + 1, 1ull);
-    }
-}
-
-__global__ __launch_bounds__(256) void lcc_write_kernel(const int* __restrict__ parent, int n,
-                                                        const unsigned long long* __restrict__ ctrl,
-                                                        unsigned char* __restrict__ out) {
-    const unsigned u = blockIdx.x * 256u + threadIdx.x;
-    if (u >= (unsigned)n) return;
-    const int i = (int)u;
-    const unsigned long long key = ctrl[0];
-    const int best = ctrl[1] ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
-    const int p = parent[i];
-    out[i] = (best >= 0 && p >= 0 && find_plain(parent, p) == best) ? 1 : 0;
-}
-
-// ---- per-class form of select and write: one winner per class value 1 .. C - 1 (C <= MAXC) ----
-// Control words of a volume (case k of K; K = 1, k = 0 for the single volume), all cleared by one memset before launch 1:
-// ctrl[k * C + c] = max key over the roots of class c, ctrl[(K + k) * C + c] = number of roots (components) of class c,
-// ctrl[(2 K + k) * C + c] = sum of their areas (voxels of class c).  Word c = 0 of every group stays zero.
-constexpr int MAXC = 8;
-
-// 1 .. C - 1, or 0 for a value that belongs to no class (0, negative, >= C)
-__device__ __forceinline__ int class_of(long long v, int C) { return (v > 0 && v < C) ? (int)v : 0; }
-
-struct ClassAcc {                                 // a thread's running key, root count and area sum per class: registers
-    unsigned long long key[MAXC - 1];
-    unsigned cnt[MAXC - 1], vox[MAXC - 1];        // a sum of areas of distinct roots never exceeds the voxel count < 2^31
-};
-
-template <bool STATS>
-__device__ __forceinline__ void class_add(ClassAcc& a, int c, int i, int ar) {
-    const unsigned long long key = ((unsigned long long)(unsigned)ar << 32) | (unsigned)(0x7fffffff - i);
-#pragma unroll
-    for (int j = 0; j < MAXC - 1; ++j)
-        if (c == j + 1) {
-            a.key[j] = umax64(a.key[j], key);
-            if (STATS) { a.cnt[j] += 1u; a.vox[j] += (unsigned)ar; }
-        }
-}
-
-// wave reduce with __shfl_xor, block reduce through LDS, then thread j commits class j + 1: at most one atomicMax (and, with
-// STATS, two integer atomicAdd) per (block, class), none where the block saw no root of the class
-template <bool STATS>
-__device__ __forceinline__ void class_commit(ClassAcc& a, int C, unsigned long long* __restrict__ keys,
-                                             unsigned long long* __restrict__ cnts, unsigned long long* __restrict__ voxs) {
-    __shared__ unsigned long long sk[4][MAXC - 1];
-    __shared__ unsigned sc[4][MAXC - 1], sv[4][MAXC - 1];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < MAXC - 1; ++j) {
-        if (j >= C - 1) break;                    // uniform
-        unsigned long long key = a.key[j];
-        unsigned cn = a.cnt[j], vx = a.vox[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            key = umax64(key, __shfl_xor(key, o));
-            if (STATS) { cn += __shfl_xor(cn, o); vx += __shfl_xor(vx, o); }
-        }
-        if (lane == 0) {
-            sk[wid][j] = key;
-            if (STATS) { sc[wid][j] = cn; sv[wid][j] = vx; }
-        }
+    for (int z = 0; z < TZ; ++z) {
+        const int e = e0 + z * LZ;
+        long long v = 0;
+        if (z < depth) v = g.v[off0 + z * slab_stride];
+        val[e] = v;
+        lp[e] = v != 0 ? e : -1;
+        cnt[e] = 0;
     }
     __syncthreads();
-    const int j = threadIdx.x;
-    if (j < C - 1) {
-        const unsigned long long key = umax64(umax64(sk[0][j], sk[1][j]), umax64(sk[2][j], sk[3][j]));
-        if (key) atomicMax(keys + j + 1, key);
-        if (STATS) {
-            const unsigned cn = sc[0][j] + sc[1][j] + sc[2][j] + sc[3][j], vx = sv[0][j] + sv[1][j] + sv[2][j] + sv[3][j];
-            if (cn) atomicAdd(cnts + j + 1, (unsigned long long)cn);
-            if (vx) atomicAdd(voxs + j + 1, (unsigned long long)vx);
-        }
-    }
-}
-
-// best[c] = the chosen root of class c, -1 where the class has no root (key 0) and for c = 0; then a block barrier
-__device__ __forceinline__ void class_best(const unsigned long long* __restrict__ keys, int C, int* best) {
-    const int c = threadIdx.x;
-    if (c < MAXC) {
-        const unsigned long long key = (c >= 1 && c < C) ? keys[c] : 0ull;
-        best[c] = key ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
-    }
-    __syncthreads();
-}
-
-// stats[c][0..2] = components, voxels, voxels of the kept component of class c; row 0 zeros (threads 0 .. C - 1 of one block)
-__device__ __forceinline__ void class_stats(const unsigned long long* __restrict__ keys,
-                                            const unsigned long long* __restrict__ cnts,
-                                            const unsigned long long* __restrict__ voxs, int C, long long* __restrict__ stats) {
-    const int c = threadIdx.x;
-    if (c >= C) return;
-    stats[3 * c] = c ? (long long)cnts[c] : 0;
-    stats[3 * c + 1] = c ? (long long)voxs[c] : 0;
-    stats[3 * c + 2] = c ? (long long)(keys[c] >> 32) : 0;
-}
-
-// the value is read at the roots only, as in lcc_select_kernel
-template <bool STATS>
-__global__ __launch_bounds__(256) void lcc_select_classes_kernel(Vol g, const int* __restrict__ parent,
-                                                                 const int* __restrict__ area, int n, int C,
-                                                                 unsigned long long* __restrict__ ctrl) {
-    ClassAcc a = {};
-    const int plane = g.d1 * g.d2;
-    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
-        const int i = (int)u;
-        if (parent[i] != i) continue;
-        const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
-        const int c = class_of(g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2], C);
-        if (c) class_add<STATS>(a, c, i, area[i]);
-    }
-    class_commit<STATS>(a, C, ctrl, ctrl + C, ctrl + 2 * C);
-}
-
-// out[i] = the voxel's own value v where v is a class and find(i) is the chosen root of that class, 0 elsewhere
-__global__ __launch_bounds__(256) void lcc_write_classes_kernel(Vol g, const int* __restrict__ parent, int n, int C,
-                                                                const unsigned long long* __restrict__ ctrl,
-                                                                unsigned char* __restrict__ out, long long* __restrict__ stats) {
-    __shared__ int best[MAXC];
-    class_best(ctrl, C, best);
-    if (stats && blockIdx.x == 0) class_stats(ctrl, ctrl + C, ctrl + 2 * C, C, stats);
-    const unsigned u = blockIdx.x * 256u + threadIdx.x;
-    if (u >= (unsigned)n) return;
-    const int i = (int)u, p = parent[i];
-    int o = 0;
-    if (p >= 0) {
-        const int plane = g.d1 * g.d2;
-        const int i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2, i2 = r - i1 * g.d2;
-        const int c = class_of(g.v[(long)i0 * g.s0 + (long)i1 * g.s1 + (long)i2 * g.s2], C);
-        if (c && best[c] >= 0 && find_plain(parent, p) == best[c]) o = c;
-    }
-    out[i] = (unsigned char)o;
-}
-
-// ---- confusion sums: out[0..3] = N, sum P*T, sum P, sum T (int64, order-independent atomics) ----
-struct Operand {
-    const void* p;
-    long s0, s1, s2;
-};
-
-template <typename TP, typename TT>
-__global__ __launch_bounds__(256) void confusion_kernel(Operand P, Operand T, int d1, int d2, int n,
-                                                        long long* __restrict__ out) {
-    __shared__ long long sm[3][4];
-    const TP* pp = static_cast<const TP*>(P.p);
-    const TT* tp = static_cast<const TT*>(T.p);
-    const int plane = d1 * d2;
-    long long spt = 0, sp = 0, st = 0;
-    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
-        const int i = (int)u, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
-        const long long a = (long long)pp[(long)i0 * P.s0 + (long)i1 * P.s1 + (long)i2 * P.s2];
-        const long long b = (long long)tp[(long)i0 * T.s0 + (long)i1 * T.s1 + (long)i2 * T.s2];
-        spt += a * b; sp += a; st += b;
-    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        spt += __shfl_xor(spt, o);
-        sp += __shfl_xor(sp, o);
-        st += __shfl_xor(st, o);
+    for (int z = 0; z < TZ; ++z) {
+        int l0, l1, l2;
+        to_logical<SLAB>(z, p, q, l0, l1, l2);
+        const int e = e0 + z * LZ;
+        const long long v = val[e];
+        if (v == 0) continue;
+        if (l2 > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
+        if (l1 > 0 && val[e - L1] == v) lds_unite(lp, e - L1, e);
+        if (l0 > 0 && val[e - L0] == v) lds_unite(lp, e - L0, e);
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wid] = spt; sm[1][wid] = sp; sm[2][wid] = st; }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        const long long s = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
-        atomicAdd(reinterpret_cast<unsigned long long*>(out + 1 + threadIdx.x), (unsigned long long)s);
+    int root[TZ];
+#pragma unroll
+    for (int z = 0; z < TZ; ++z) {
+        const int e = e0 + z * LZ;
+        root[z] = val[e] != 0 ? lds_find(lp, e) : -1;
+        if (root[z] >= 0) atomicAdd(&cnt[root[z]], 1);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 3) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)n);
+    __syncthreads();
+#pragma unroll
+    for (int z = 0; z < TZ; ++z) {
+        if (z >= depth) break;
+        int gr = -1;
+        if (root[z] >= 0) {                       // the tile-blob's lowest local index is its first voxel: its lowest node
+            const int r = root[z], r0 = r / L0, r1 = (r / L1) & (TQ - 1), r2 = r & (L1 - 1);
+            gr = g.node(o0 + r0, o1 + r1, o2 + r2);
+        }
+        parent[node0 + z * slab_nodes] = gr;
+        area[node0 + z * slab_nodes] = cnt[e0 + z * LZ];
+    }
 }
 
-bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
-    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
-    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
-}
-
-
-// ---- batched over K ragged cases -------------------------------------------------------------------------------------
-struct Cases {
-    const long long* v;       // [S_total][H][W], contiguous
-    const long long* start;   // [K + 1] first slice of every case (device)
-    int S_total, H, W;
-    int tw;                   // 16-wide tiles along w
-};
-
-// slices [s0, s0 + ns) of case k; a table entry outside [0, S_total] or below its predecessor is clamped, so that no
-// address derived from it leaves the buffers
-__device__ __forceinline__ void case_range(const long long* start, int k, int S_total, int& s0, int& ns) {
-    long long a = start[k], b = start[k + 1];
-    a = a < 0 ? 0 : (a > S_total ? S_total : a);
-    b = b < a ? a : (b > S_total ? S_total : b);
-    s0 = (int)a;
-    ns = (int)(b - a);
-}
-
-// a 16 x 16 (h, w) tile of the plane per block, 4 slices at a time: thread t owns (h, w) = (t / 16, t % 16), local index
-// e = t * 4 + z -- (h, w, s) order, the raster order of the case
-__global__ __launch_bounds__(256) void lccb_local_kernel(Cases g, int* __restrict__ parent, int* __restrict__ area,
-                                                         unsigned long long* __restrict__ ctrl) {
+template <class G>
+__global__ __launch_bounds__(256) void lcc_local_kernel(G geo, int* __restrict__ parent, int* __restrict__ area,
+                                                        unsigned long long* __restrict__ ctrl) {
     __shared__ long long val[TILE];
     __shared__ int lp[TILE];
     __shared__ int cnt[TILE];
-    const int k = blockIdx.y, t = threadIdx.x, hl = t >> 4, wl = t & 15;
-    if (blockIdx.x == 0 && t == 0) { ctrl[2 * k] = 0ull; ctrl[2 * k + 1] = 0ull; }
-    int s0, ns;
-    case_range(g.start, k, g.S_total, s0, ns);
-    const int h = (int)(blockIdx.x / g.tw) * 16 + hl, w = (int)(blockIdx.x % g.tw) * 16 + wl;
-    const bool in_hw = h < g.H && w < g.W;
-    const long hw = (long)g.H * g.W;
-    const int base = (int)(s0 * hw), col = in_hw ? (h * g.W + w) * ns : 0;
-    for (int sc = 0; sc < ns; sc += TZ) {
-        __syncthreads();                          // the previous chunk's LDS is read to the end
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = t * TZ + z;
-            long long v = 0;
-            if (in_hw && sc + z < ns) v = g.v[(long)(s0 + sc + z) * hw + (long)h * g.W + w];
-            val[e] = v;
-            lp[e] = v != 0 ? e : -1;
-            cnt[e] = 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = t * TZ + z;
-            const long long v = val[e];
-            if (v == 0) continue;
-            if (z > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
-            if (wl > 0 && val[e - TZ] == v) lds_unite(lp, e - TZ, e);
-            if (hl > 0 && val[e - 16 * TZ] == v) lds_unite(lp, e - 16 * TZ, e);
-        }
-        __syncthreads();
-        int root[TZ];
-#pragma unroll
-        for (int z = 0; z < TZ; ++z) {
-            const int e = t * TZ + z;
-            root[z] = val[e] != 0 ? lds_find(lp, e) : -1;
-            if (root[z] >= 0) atomicAdd(&cnt[root[z]], 1);
-        }
-        __syncthreads();
-        if (in_hw) {
-#pragma unroll
-            for (int z = 0; z < TZ; ++z) {
-                if (sc + z >= ns) break;
-                const int e = t * TZ + z;
-                int gr = -1;
-                if (root[z] >= 0) {               // the lowest local index of the tile-blob is its lowest node
-                    const int r = root[z], rt = r / TZ, rh = rt >> 4, rw = rt & 15;
-                    gr = base + ((h - hl + rh) * g.W + (w - wl + rw)) * ns + sc + (r - rt * TZ);
-                }
-                parent[base + col + sc + z] = gr;
-                area[base + col + sc + z] = cnt[e];
-            }
-        }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[2 * blockIdx.y] = 0ull; ctrl[2 * blockIdx.y + 1] = 0ull; }
+    const View g = geo.view();
+    for (int tile = geo.tile_begin(); tile < geo.tile_end(g); tile += geo.tile_step()) {
+        int o0, o1, o2;
+        geo.tile_origin(tile, o0, o1, o2);
+        tile_local<G::SLAB>(g, o0, o1, o2, parent, area, val, lp, cnt);
     }
 }
 
-// lower faces of every 16 x 16 x 4 chunk: w face (4 x 16 pairs), h face (4 x 16), s face (16 x 16)
-__global__ __launch_bounds__(256) void lccb_border_kernel(Cases g, int* __restrict__ parent) {
-    const int k = blockIdx.y;
-    int s0, ns;
-    case_range(g.start, k, g.S_total, s0, ns);
-    const int h0 = (int)(blockIdx.x / g.tw) * 16, w0 = (int)(blockIdx.x % g.tw) * 16;
-    const long hw = (long)g.H * g.W;
-    const int base = (int)(s0 * hw);
-    for (int sc = 0; sc < ns; sc += TZ) {
-        for (int q = threadIdx.x; q < 2 * TZ * 16 + 256; q += 256) {
-            int z, hl, wl, dz = 0, dh = 0, dw = 0;
-            if (q < TZ * 16) {
-                if (w0 == 0) continue;
-                z = q >> 4; hl = q & 15; wl = 0; dw = 1;
-            } else if (q < 2 * TZ * 16) {
-                if (h0 == 0) continue;
-                const int j = q - TZ * 16;
-                z = j >> 4; wl = j & 15; hl = 0; dh = 1;
-            } else {
-                if (sc == 0) continue;
-                const int j = q - 2 * TZ * 16;
-                hl = j >> 4; wl = j & 15; z = 0; dz = 1;
-            }
-            const int s = sc + z, h = h0 + hl, w = w0 + wl;
-            if (s >= ns || h >= g.H || w >= g.W) continue;
-            const long off = (long)(s0 + s) * hw + (long)h * g.W + w;
-            const long long v = g.v[off];
-            if (v == 0) continue;
-            if (g.v[off - dz * hw - dh * g.W - dw] != v) continue;
-            const int gi = base + (h * g.W + w) * ns + s;
-            unite(parent, gi - dz - (dh * g.W + dw) * ns, gi);
+// ---- 2 border: the three lower faces of a tile, in thread coordinates: q face (TZ x 16 pairs), p face (TZ x 16),
+// z face (16 x 16) ----
+template <int SLAB>
+__device__ __forceinline__ void tile_border(const View& g, int o0, int o1, int o2, int* __restrict__ parent) {
+    for (int k = threadIdx.x; k < 2 * TZ * TQ + TQ * TQ; k += 256) {
+        int z, p, q, dz = 0, dp = 0, dq = 0;
+        if (k < TZ * TQ) {
+            z = k >> 4; p = k & 15; q = 0; dq = 1;
+        } else if (k < 2 * TZ * TQ) {
+            const int j = k - TZ * TQ;
+            z = j >> 4; q = j & 15; p = 0; dp = 1;
+        } else {
+            const int j = k - 2 * TZ * TQ;
+            p = j >> 4; q = j & 15; z = 0; dz = 1;
         }
+        int l0, l1, l2, e0, e1, e2;
+        to_logical<SLAB>(z, p, q, l0, l1, l2);
+        to_logical<SLAB>(dz, dp, dq, e0, e1, e2);
+        const int a0 = o0 + l0, a1 = o1 + l1, a2 = o2 + l2;
+        if (a0 < e0 || a1 < e1 || a2 < e2) continue;          // the face lies on the volume's edge
+        if (!g.has(a0, a1, a2)) continue;
+        const long off = g.off(a0, a1, a2);
+        const long long v = g.v[off];
+        if (v == 0) continue;
+        if (g.v[off - g.off(e0, e1, e2)] != v) continue;
+        unite(parent, g.node(a0 - e0, a1 - e1, a2 - e2), g.node(a0, a1, a2));
     }
 }
 
-// the nodes of 256 plane positions of a case are one contiguous run: (see lcc_count_kernel)
-__global__ __launch_bounds__(256) void lccb_count_kernel(const long long* __restrict__ start, int S_total, int HW,
-                                                         int* __restrict__ parent, int* __restrict__ area) {
-    int s0, ns;
-    case_range(start, blockIdx.y, S_total, s0, ns);
-    const int p0 = (int)blockIdx.x * 256, np = min(256, HW - p0);
-    const int first = (int)((long)s0 * HW) + p0 * ns, count = np * ns;
-    for (int o = 0; o < count; o += 256) {        // whole waves: the trip count is the block's
+template <class G>
+__global__ __launch_bounds__(256) void lcc_border_kernel(G geo, int* __restrict__ parent) {
+    const View g = geo.view();
+    for (int tile = geo.tile_begin(); tile < geo.tile_end(g); tile += geo.tile_step()) {
+        int o0, o1, o2;
+        geo.tile_origin(tile, o0, o1, o2);
+        tile_border<G::SLAB>(g, o0, o1, o2, parent);
+    }
+}
+
+// ---- 3 count: tile-blob roots that were joined to another set add their area to its root.  Lanes of one wave that add
+// to the same root are summed first: one atomic per (wave, root).  Whole waves: the trip count is the block's ----
+template <class G>
+__global__ __launch_bounds__(256) void lcc_count_kernel(G geo, int* __restrict__ parent, int* __restrict__ area) {
+    const View g = geo.view();
+    int first, count;
+    geo.count_run(g, first, count);
+    for (int o = 0; o < count; o += 256) {
         const int j = o + (int)threadIdx.x, i = first + j;
         int a = 0, r = -1;
         if (j < count) {
@@ -579,108 +338,194 @@ __global__ __launch_bounds__(256) void lccb_count_kernel(const long long* __rest
     }
 }
 
-// thread = one plane position of the case, all its slices (consecutive nodes); ctrl[2k] = max key, ctrl[2k + 1] = positive flag
-__global__ __launch_bounds__(256) void lccb_select_kernel(Cases g, const int* __restrict__ parent, const int* __restrict__ area,
-                                                          unsigned long long* __restrict__ ctrl) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    const int k = blockIdx.y;
-    int s0, ns;
-    case_range(g.start, k, g.S_total, s0, ns);
-    const long hw = (long)g.H * g.W;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long key = 0;
-    int pos = 0;
-    if (p < hw) {
-        const int first = (int)(s0 * hw + p * ns);
-        for (int s = 0; s < ns; ++s) {
-            const int i = first + s;
-            if (parent[i] != i) continue;
-            key = umax64(key, ((unsigned long long)(unsigned)area[i] << 32) | (unsigned)(0x7fffffff - i));
-            if (!pos) pos = g.v[(long)(s0 + s) * hw + p] > 0;
+// ---- 4 select, 5 write ----
+// Control words of case k = blockIdx.y of K = gridDim.y (the single volume: k = 0, K = 1), by slot.
+// BINARY, one slot: ctrl[2 k] = max key over the roots, ctrl[2 k + 1] = 1 when some root (so some voxel) holds a positive
+// value.  CLASSES, slot j = class j + 1 <= C - 1 <= MAXC - 1: ctrl[k * C + c] = max key over the roots of class c,
+// ctrl[(K + k) * C + c] = number of roots (components) of class c, ctrl[(2 K + k) * C + c] = sum of their areas (voxels of
+// class c); word c = 0 of every group stays zero.  CLASSES_STATS: CLASSES that also fills the counts and the sums.
+enum Mode { BINARY, CLASSES, CLASSES_STATS };
+constexpr int MAXC = 8;
+template <Mode M> constexpr int SLOTS = M == BINARY ? 1 : MAXC - 1;
+
+struct Ctrl { long key, cnt, vox; };              // word of slot 0
+template <Mode M>
+__device__ __forceinline__ Ctrl ctrl_words(int C) {
+    const long k = blockIdx.y, K = gridDim.y;
+    if (M == BINARY) return Ctrl{2 * k, 2 * k + 1, 0};
+    return Ctrl{k * C + 1, (K + k) * C + 1, (2 * K + k) * C + 1};
+}
+
+// 1 .. C - 1, or 0 for a value that belongs to no class (0, negative, >= C)
+__device__ __forceinline__ int class_of(long long v, int C) { return (v > 0 && v < C) ? (int)v : 0; }
+
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+template <Mode M>
+struct Acc {                                      // a thread's running key, root count and area sum per slot: registers
+    unsigned long long key[SLOTS<M>];
+    unsigned cnt[SLOTS<M>], vox[SLOTS<M>];        // a sum of areas of distinct roots never exceeds the voxel count < 2^31
+};
+
+// root i of area ar goes to `slot`: larger area first, then the lower root
+template <Mode M>
+__device__ __forceinline__ void acc_add(Acc<M>& a, int slot, int i, int ar) {
+    const unsigned long long key = ((unsigned long long)(unsigned)ar << 32) | (unsigned)(0x7fffffff - i);
+#pragma unroll
+    for (int j = 0; j < SLOTS<M>; ++j)
+        if (slot == j) {
+            a.key[j] = umax64(a.key[j], key);
+            if (M == CLASSES_STATS) { a.cnt[j] += 1u; a.vox[j] += (unsigned)ar; }
+        }
+}
+
+// wave reduce with __shfl_xor, block reduce through LDS, then thread j commits slot j: at most one atomicMax (and the flag's,
+// or with the stats two integer atomicAdd) per (block, slot), none where the block saw no root of the slot
+template <Mode M>
+__device__ __forceinline__ void acc_commit(Acc<M>& a, int live, unsigned long long* __restrict__ ctrl, const Ctrl w) {
+    __shared__ unsigned long long sk[4][SLOTS<M>];
+    __shared__ unsigned sc[4][SLOTS<M>], sv[4][SLOTS<M>];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < SLOTS<M>; ++j) {
+        if (j >= live) break;                     // uniform
+        unsigned long long key = a.key[j];
+        unsigned cn = a.cnt[j], vx = a.vox[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            key = umax64(key, __shfl_xor(key, o));
+            if (M != CLASSES) cn += __shfl_xor(cn, o);
+            if (M == CLASSES_STATS) vx += __shfl_xor(vx, o);
+        }
+        if (lane == 0) {
+            sk[wid][j] = key;
+            if (M != CLASSES) sc[wid][j] = cn;
+            if (M == CLASSES_STATS) sv[wid][j] = vx;
         }
     }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j < live) {
+        const unsigned long long key = umax64(umax64(sk[0][j], sk[1][j]), umax64(sk[2][j], sk[3][j]));
+        if (key) atomicMax(ctrl + w.key + j, key);
+        if (M != CLASSES) {
+            const unsigned cn = sc[0][j] + sc[1][j] + sc[2][j] + sc[3][j];
+            if (M == BINARY) { if (cn) atomicMax(ctrl + w.cnt + j, 1ull); }
+            else if (cn) atomicAdd(ctrl + w.cnt + j, (unsigned long long)cn);
+        }
+        if (M == CLASSES_STATS) {
+            const unsigned vx = sv[0][j] + sv[1][j] + sv[2][j] + sv[3][j];
+            if (vx) atomicAdd(ctrl + w.vox + j, (unsigned long long)vx);
+        }
+    }
+}
+
+// the chosen root of a slot, -1 where it has none (key 0; BINARY: no positive voxel either)
+template <Mode M>
+__device__ __forceinline__ int chosen_root(const unsigned long long* __restrict__ ctrl, const Ctrl& w, int slot) {
+    const unsigned long long key = ctrl[w.key + slot], flag = M == BINARY ? ctrl[w.cnt + slot] : 1ull;   // (one load for both)
+    return (key && flag) ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffull) : -1;
+}
+
+// voxel with tile-blob root p (-1: background) belongs to the component of root `best`
+__device__ __forceinline__ bool kept(const int* __restrict__ parent, int p, int best) {
+    return best >= 0 && p >= 0 && find_plain(parent, p) == best;
+}
+
+// the value is read at the roots only
+template <class G, Mode M>
+__global__ __launch_bounds__(256) void lcc_select_kernel(G geo, const int* __restrict__ parent, const int* __restrict__ area,
+                                                         int C, unsigned long long* __restrict__ ctrl) {
+    const View g = geo.view();
+    Acc<M> a = {};
+    geo.select_nodes(g, [&](int i, auto value_off, long) {
+        if (parent[i] != i) return;
+        if (M == BINARY) {
+            acc_add(a, 0, i, area[i]);
+            if (!a.cnt[0]) a.cnt[0] = g.v[value_off()] > 0;
+        } else {
+            const int c = class_of(g.v[value_off()], C);
+            if (c) acc_add(a, c - 1, i, area[i]);
+        }
+    });
+    acc_commit(a, M == BINARY ? 1 : C - 1, ctrl, ctrl_words<M>(C));
+}
+
+// BINARY: out[i] = 1 where find(i) is the chosen root.  CLASSES: out[i] = the voxel's own value v where v is a class and
+// find(i) is the chosen root of that class; stats[k][c][0..2] = components, voxels, voxels of the kept component of class c,
+// row 0 zeros (threads 0 .. C - 1 of the case's first block).  0 elsewhere
+template <class G, Mode M>
+__global__ __launch_bounds__(256) void lcc_write_kernel(G geo, const int* __restrict__ parent, int C,
+                                                        const unsigned long long* __restrict__ ctrl,
+                                                        unsigned char* __restrict__ out, long long* __restrict__ stats) {
+    __shared__ int best[MAXC];
+    const Ctrl w = ctrl_words<M>(C);
+    const int c = threadIdx.x;
+    int only = -1;
+    if (M == BINARY) {
+        only = chosen_root<M>(ctrl, w, 0);
+    } else {
+        if (c < MAXC) best[c] = (c >= 1 && c < C) ? chosen_root<M>(ctrl, w, c - 1) : -1;
+        if (stats && blockIdx.x == 0 && c < C) {
+            long long* st = stats + ((long)blockIdx.y * C + c) * 3;
+            st[0] = c ? (long long)ctrl[w.cnt + c - 1] : 0;
+            st[1] = c ? (long long)ctrl[w.vox + c - 1] : 0;
+            st[2] = c ? (long long)(ctrl[w.key + c - 1] >> 32) : 0;
+        }
+        __syncthreads();
+    }
+    const View g = geo.view();
+    geo.write_nodes(g, [&](int i, auto value_off, long at) {
+        const int p = parent[i];
+        int o;
+        if (M == BINARY) {
+            o = kept(parent, p, only);
+        } else {
+            const int cv = p >= 0 ? class_of(g.v[value_off()], C) : 0;
+            o = (cv && kept(parent, p, best[cv])) ? cv : 0;
+        }
+        out[at] = (unsigned char)o;
+    });
+}
+
+// ---- confusion sums: out[0..3] = N, sum P*T, sum P, sum T (int64, order-independent atomics) ----
+// three block sums: thread j < 3 returns the block's j-th total, every other thread 0
+__device__ __forceinline__ long long block_sum3(long long s0, long long s1, long long s2) {
+    __shared__ long long sm[3][4];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        key = umax64(key, __shfl_xor(key, o));
-        pos |= __shfl_xor(pos, o);
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
     }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { sk[wid] = key; sp[wid] = pos; }
+    if (lane == 0) { sm[0][wid] = s0; sm[1][wid] = s1; sm[2][wid] = s2; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        key = umax64(umax64(sk[0], sk[1]), umax64(sk[2], sk[3]));
-        pos = sp[0] | sp[1] | sp[2] | sp[3];
-        if (key) atomicMax(ctrl + 2 * k, key);
-        if (pos) atomicMax(ctrl + 2 * k + 1, 1ull);
-    }
+    if (threadIdx.x >= 3) return 0;
+    return sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
 }
 
-__global__ __launch_bounds__(256) void lccb_write_kernel(const long long* __restrict__ start, int S_total, long hw,
-                                                         const int* __restrict__ parent,
-                                                         const unsigned long long* __restrict__ ctrl,
-                                                         unsigned char* __restrict__ out) {
-    const int k = blockIdx.y;
-    int s0, ns;
-    case_range(start, k, S_total, s0, ns);
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= hw) return;
-    const int best = ctrl[2 * k + 1] ? 0x7fffffff - (int)(unsigned)(ctrl[2 * k] & 0xffffffffull) : -1;
-    const int first = (int)(s0 * hw + p * ns);
-    for (int s = 0; s < ns; ++s) {
-        const int q = parent[first + s];
-        out[(long)(s0 + s) * hw + p] = (best >= 0 && q >= 0 && find_plain(parent, q) == best) ? 1 : 0;
-    }
-}
+struct Operand {
+    const void* p;
+    long s0, s1, s2;
+};
 
-// per-class forms (see lcc_select_classes_kernel): the control words of case k are the k-th group of C in each of the three
-// runs of K * C words
-template <bool STATS>
-__global__ __launch_bounds__(256) void lccb_select_classes_kernel(Cases g, const int* __restrict__ parent,
-                                                                  const int* __restrict__ area, int C,
-                                                                  unsigned long long* __restrict__ ctrl) {
-    const int k = blockIdx.y, K = gridDim.y;
-    int s0, ns;
-    case_range(g.start, k, g.S_total, s0, ns);
-    const long hw = (long)g.H * g.W;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    ClassAcc a = {};
-    if (p < hw) {
-        const int first = (int)(s0 * hw + p * ns);
-        for (int s = 0; s < ns; ++s) {
-            const int i = first + s;
-            if (parent[i] != i) continue;
-            const int c = class_of(g.v[(long)(s0 + s) * hw + p], C);
-            if (c) class_add<STATS>(a, c, i, area[i]);
-        }
+template <typename TP, typename TT>
+__global__ __launch_bounds__(256) void confusion_kernel(Operand P, Operand T, int d1, int d2, int n,
+                                                        long long* __restrict__ out) {
+    const TP* pp = static_cast<const TP*>(P.p);
+    const TT* tp = static_cast<const TT*>(T.p);
+    const int plane = d1 * d2;
+    long long spt = 0, sp = 0, st = 0;
+    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
+        const int i = (int)u, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
+        const long long a = (long long)pp[(long)i0 * P.s0 + (long)i1 * P.s1 + (long)i2 * P.s2];
+        const long long b = (long long)tp[(long)i0 * T.s0 + (long)i1 * T.s1 + (long)i2 * T.s2];
+        spt += a * b; sp += a; st += b;
     }
-    class_commit<STATS>(a, C, ctrl + (long)k * C, ctrl + (long)(K + k) * C, ctrl + (long)(2 * K + k) * C);
-}
-
-__global__ __launch_bounds__(256) void lccb_write_classes_kernel(Cases g, const int* __restrict__ parent, int C,
-                                                                 const unsigned long long* __restrict__ ctrl,
-                                                                 unsigned char* __restrict__ out, long long* __restrict__ stats) {
-    __shared__ int best[MAXC];
-    const int k = blockIdx.y, K = gridDim.y;
-    const unsigned long long* keys = ctrl + (long)k * C;
-    class_best(keys, C, best);
-    if (stats && blockIdx.x == 0)
-        class_stats(keys, ctrl + (long)(K + k) * C, ctrl + (long)(2 * K + k) * C, C, stats + (long)k * C * 3);
-    int s0, ns;
-    case_range(g.start, k, g.S_total, s0, ns);
-    const long hw = (long)g.H * g.W;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= hw) return;
-    const int first = (int)(s0 * hw + p * ns);
-    for (int s = 0; s < ns; ++s) {
-        const int q = parent[first + s];
-        int o = 0;
-        if (q >= 0) {
-            const int c = class_of(g.v[(long)(s0 + s) * hw + p], C);
-            if (c && best[c] >= 0 && find_plain(parent, q) == best[c]) o = c;
-        }
-        out[(long)(s0 + s) * hw + p] = (unsigned char)o;
-    }
+    const long long s = block_sum3(spt, sp, st);
+    if (threadIdx.x < 3) atomicAdd(reinterpret_cast<unsigned long long*>(out + 1 + threadIdx.x), (unsigned long long)s);
+    if (blockIdx.x == 0 && threadIdx.x == 3) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)n);
 }
 
 // out[k][0..3] = N, sum p*t, sum p, sum t with t = (target byte == match); VEC: 16 bytes per load (hw % 16 == 0, aligned)
@@ -689,7 +534,6 @@ __global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned c
                                                                 const unsigned char* __restrict__ tg,
                                                                 const long long* __restrict__ start, int S_total, long hw,
                                                                 int match, long long* __restrict__ out) {
-    __shared__ long long sm[3][4];
     const int k = blockIdx.y;
     int s0, ns;
     case_range(start, k, S_total, s0, ns);
@@ -718,20 +562,16 @@ __global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned c
             spt += m ? x : 0u; sp += x; st += m;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        spt += __shfl_xor(spt, o);
-        sp += __shfl_xor(sp, o);
-        st += __shfl_xor(st, o);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wid] = spt; sm[1][wid] = sp; sm[2][wid] = st; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const long long s = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(out + 4 * k + 1 + threadIdx.x), (unsigned long long)s);
-    }
+    const long long s = block_sum3(spt, sp, st);
+    if (threadIdx.x < 3 && s) atomicAdd(reinterpret_cast<unsigned long long*>(out + 4 * k + 1 + threadIdx.x), (unsigned long long)s);
     if (blockIdx.x == 0 && threadIdx.x == 3) out[4 * k] = n;
+}
+
+// ---- host ----
+bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
+    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
+    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
+    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
 }
 
 // [S_total][H][W] with K cases: everything the grids and the node indices need fits an int
@@ -740,13 +580,87 @@ bool batch_ok(int64_t S_total, int64_t H, int64_t W, int64_t K) {
     return dims_ok(S_total, H, W);
 }
 
+bool classes_ok(int C) { return C >= 2 && C <= MAXC; }
+
+// workspace: parent[n], area[n], then, 16-byte aligned, K groups of control words
+size_t ws_bytes(int64_t nvox, int64_t K, int64_t words_per_case) {
+    if (nvox < 0 || nvox > INT32_MAX || K < 0 || K > 65535) return 0;
+    return (size_t)(2 * nvox) * sizeof(int) + 16 + (size_t)(K * words_per_case) * sizeof(unsigned long long);
+}
+
+struct Grids { dim3 tile, count, select, write; };   // launches 1 - 2, 3, 4, 5
+
+Strided make_strided(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2, Grids& gr) {
+    Strided geo;
+    geo.g = View{v, (long)s0, (long)s1, (long)s2, (int)d0, (int)d1, (int)d2, 0};
+    geo.t1 = (int)((d1 + TQ - 1) / TQ); geo.t2 = (int)((d2 + TQ - 1) / TQ);
+    geo.tiles = (int)((long)geo.t1 * geo.t2 * ((d0 + TZ - 1) / TZ));   // (<= the number of voxels)
+    const long nb = (d0 * d1 * d2 + 255) / 256;
+    gr.tile = dim3((unsigned)min((long)geo.tiles, 65536L));
+    gr.count = gr.write = dim3((unsigned)nb);
+    gr.select = dim3((unsigned)min(nb, 1024L));
+    return geo;
+}
+
+Ragged make_ragged(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H, int64_t W,
+                   Grids& gr) {
+    Ragged geo;
+    geo.v = v; geo.start = slice_start; geo.S_total = (int)S_total; geo.H = (int)H; geo.W = (int)W;
+    geo.tw = (int)((W + 15) / 16);
+    const long tiles = (long)geo.tw * ((H + 15) / 16), chunks = (H * W + 255) / 256;   // (tiles < H W / 256 + (H + W) / 16 + 2)
+    gr.tile = dim3((unsigned)tiles, (unsigned)K);
+    gr.count = gr.select = gr.write = dim3((unsigned)chunks, (unsigned)K);
+    return geo;
+}
+
+// the five launches over n nodes and K cases; C = 0: BINARY, else the per-class form with one memset in front
+template <class G>
+int lcc_launch(const G& geo, const Grids& gr, int n, int64_t K, int C, unsigned char* out, long long* stats, void* ws,
+               hipStream_t stream) {
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    int* parent = static_cast<int*>(ws);
+    int* area = parent + n;
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    const int* cparent = parent;
+    const int* carea = area;
+    const unsigned long long* cctrl = ctrl;
+    const dim3 block(256);
+    if (C) {
+        hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(3 * K * C) * sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    const double bytes = 29.0 * n;   // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, select 4, write 4 + 1
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel<G>, gr.tile, block, 0, stream, geo, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel<G>, gr.tile, block, 0, stream, geo, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel<G>, gr.count, block, 0, stream, geo, parent, area);
+    if (!C)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<G, BINARY>), gr.select, block, 0, stream, geo, cparent, carea, C, ctrl);
+    else if (stats)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<G, CLASSES_STATS>), gr.select, block, 0, stream, geo, cparent, carea, C, ctrl);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<G, CLASSES>), gr.select, block, 0, stream, geo, cparent, carea, C, ctrl);
+    if (!C)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_write_kernel<G, BINARY>), gr.write, block, 0, stream, geo, cparent, C, cctrl, out, stats);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_write_kernel<G, CLASSES>), gr.write, block, 0, stream, geo, cparent, C, cctrl, out, stats);
+    return aide_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
 
-size_t aide_lcc3d_ws_bytes(int64_t nvox) {
-    if (nvox < 0 || nvox > INT32_MAX) return 0;
-    return (size_t)(2 * nvox) * sizeof(int) + 16 + 2 * sizeof(unsigned long long);
+size_t aide_lcc3d_ws_bytes(int64_t nvox) { return ws_bytes(nvox, 1, 2); }
+
+size_t aide_lcc3d_classes_ws_bytes(int64_t nvox, int num_classes) {
+    return classes_ok(num_classes) ? ws_bytes(nvox, 1, 3 * num_classes) : 0;
+}
+
+size_t aide_lcc3d_batched_ws_bytes(int64_t nvox_total, int64_t K) { return ws_bytes(nvox_total, K, 2); }
+
+size_t aide_lcc3d_classes_batched_ws_bytes(int64_t nvox_total, int64_t K, int num_classes) {
+    return classes_ok(num_classes) ? ws_bytes(nvox_total, K, 3 * num_classes) : 0;
 }
 
 int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
@@ -755,73 +669,49 @@ int aide_keep_largest_cc3d(const long long* v, int64_t d0, int64_t d1, int64_t d
     const int n = (int)(d0 * d1 * d2);
     if (n == 0) return 0;
     if (!v || !out || !ws) return AIDE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
-    int* parent = static_cast<int*>(ws);
-    int* area = parent + n;
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
-    Vol g;
-    g.v = v; g.s0 = (long)s0; g.s1 = (long)s1; g.s2 = (long)s2;
-    g.d0 = (int)d0; g.d1 = (int)d1; g.d2 = (int)d2;
-    g.tx = (int)((d2 + TX - 1) / TX); g.ty = (int)((d1 + TY - 1) / TY);
-    const long tiles = (long)g.tx * g.ty * ((d0 + TZ - 1) / TZ);
-    const unsigned nb = (unsigned)(((long)n + 255) / 256);
-    const unsigned ntile = (unsigned)min(tiles, 65536L);
-    const unsigned nsel = (unsigned)min((long)nb, 1024L);
-    const double bytes = 29.0 * n;   // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, select 4, write 4 + 1
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent, area, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel, dim3(nb), dim3(256), 0, stream, parent, area, n);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_kernel, dim3(nsel), dim3(256), 0, stream, g,
-                      (const int*)parent, (const int*)area, n, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_write_kernel, dim3(nb), dim3(256), 0, stream, (const int*)parent, n,
-                      (const unsigned long long*)ctrl, out);
-    return aide_launch_status();
+    Grids gr;
+    const Strided geo = make_strided(v, d0, d1, d2, s0, s1, s2, gr);
+    return lcc_launch(geo, gr, n, 1, 0, out, nullptr, ws, stream);
 }
 
-size_t aide_lcc3d_classes_ws_bytes(int64_t nvox, int num_classes) {
-    if (nvox < 0 || nvox > INT32_MAX || num_classes < 2 || num_classes > MAXC) return 0;
-    return (size_t)(2 * nvox) * sizeof(int) + 16 + (size_t)(3 * num_classes) * sizeof(unsigned long long);
-}
-
-// launches 1 - 3 are the binary form's, unchanged; one memset clears the 3 C control words before them
 int aide_keep_largest_cc3d_classes(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
                                    int num_classes, unsigned char* out, long long* stats, void* ws, hipStream_t stream) {
-    if (num_classes < 2 || num_classes > MAXC || !dims_ok(d0, d1, d2)) return AIDE_ERR_ARG;
-    const int n = (int)(d0 * d1 * d2), C = num_classes;
+    if (!classes_ok(num_classes) || !dims_ok(d0, d1, d2)) return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
     if (n == 0) {
         if (!stats) return 0;
-        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * C) * sizeof(long long), stream);
+        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * num_classes) * sizeof(long long), stream);
     }
     if (!v || !out || !ws) return AIDE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
-    int* parent = static_cast<int*>(ws);
-    int* area = parent + n;
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
-    Vol g;
-    g.v = v; g.s0 = (long)s0; g.s1 = (long)s1; g.s2 = (long)s2;
-    g.d0 = (int)d0; g.d1 = (int)d1; g.d2 = (int)d2;
-    g.tx = (int)((d2 + TX - 1) / TX); g.ty = (int)((d1 + TY - 1) / TY);
-    const long tiles = (long)g.tx * g.ty * ((d0 + TZ - 1) / TZ);
-    const unsigned nb = (unsigned)(((long)n + 255) / 256);
-    const unsigned ntile = (unsigned)min(tiles, 65536L);
-    const unsigned nsel = (unsigned)min((long)nb, 1024L);
-    hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(3 * C) * sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return (int)e;
-    const double bytes = 29.0 * n;
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent, area, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel, dim3(ntile), dim3(256), 0, stream, g, tiles, parent);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel, dim3(nb), dim3(256), 0, stream, parent, area, n);
-    if (stats)
-        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_classes_kernel<true>, dim3(nsel), dim3(256), 0, stream, g,
-                          (const int*)parent, (const int*)area, n, C, ctrl);
-    else
-        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_select_classes_kernel<false>, dim3(nsel), dim3(256), 0, stream, g,
-                          (const int*)parent, (const int*)area, n, C, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_write_classes_kernel, dim3(nb), dim3(256), 0, stream, g, (const int*)parent, n, C,
-                      (const unsigned long long*)ctrl, out, stats);
-    return aide_launch_status();
+    Grids gr;
+    const Strided geo = make_strided(v, d0, d1, d2, s0, s1, s2, gr);
+    return lcc_launch(geo, gr, n, 1, num_classes, out, stats, ws, stream);
+}
+
+int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H,
+                                   int64_t W, unsigned char* out, void* ws, hipStream_t stream) {
+    if (!batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
+    const int n = (int)(S_total * H * W);
+    if (n == 0 || K == 0) return 0;
+    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
+    Grids gr;
+    const Ragged geo = make_ragged(v, slice_start, K, S_total, H, W, gr);
+    return lcc_launch(geo, gr, n, K, 0, out, nullptr, ws, stream);
+}
+
+int aide_keep_largest_cc3d_classes_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total,
+                                           int64_t H, int64_t W, int num_classes, unsigned char* out, long long* stats,
+                                           void* ws, hipStream_t stream) {
+    if (!classes_ok(num_classes) || !batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
+    const int n = (int)(S_total * H * W);
+    if (n == 0 || K == 0) {
+        if (!stats || K == 0) return 0;
+        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * K * num_classes) * sizeof(long long), stream);
+    }
+    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
+    Grids gr;
+    const Ragged geo = make_ragged(v, slice_start, K, S_total, H, W, gr);
+    return lcc_launch(geo, gr, n, K, num_classes, out, stats, ws, stream);
 }
 
 int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
@@ -844,82 +734,6 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
         AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 9.0 * n, (confusion_kernel<long long, unsigned char>), grid, block, 0, stream, P, T, e1, e2, n, out);
     else
         AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 16.0 * n, (confusion_kernel<long long, long long>), grid, block, 0, stream, P, T, e1, e2, n, out);
-    return aide_launch_status();
-}
-
-size_t aide_lcc3d_batched_ws_bytes(int64_t nvox_total, int64_t K) {
-    if (nvox_total < 0 || nvox_total > INT32_MAX || K < 0 || K > 65535) return 0;
-    return (size_t)(2 * nvox_total) * sizeof(int) + 16 + (size_t)(2 * K) * sizeof(unsigned long long);
-}
-
-int aide_keep_largest_cc3d_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total, int64_t H,
-                                   int64_t W, unsigned char* out, void* ws, hipStream_t stream) {
-    if (!batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
-    const int n = (int)(S_total * H * W);
-    if (n == 0 || K == 0) return 0;
-    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
-    int* parent = static_cast<int*>(ws);
-    int* area = parent + n;
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
-    Cases g;
-    g.v = v; g.start = slice_start; g.S_total = (int)S_total; g.H = (int)H; g.W = (int)W;
-    g.tw = (int)((W + 15) / 16);
-    const long tiles = (long)g.tw * ((H + 15) / 16), chunks = (H * W + 255) / 256;
-    if (tiles > INT32_MAX) return AIDE_ERR_ARG;
-    const dim3 gt((unsigned)tiles, (unsigned)K), gc((unsigned)chunks, (unsigned)K), block(256);
-    const int hw = (int)(H * W);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 29.0 * n, lccb_local_kernel, gt, block, 0, stream, g, parent, area, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_border_kernel, gt, block, 0, stream, g, parent);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_count_kernel, gc, block, 0, stream, slice_start, (int)S_total, hw, parent, area);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_kernel, gc, block, 0, stream, g, (const int*)parent, (const int*)area,
-                      ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_write_kernel, gc, block, 0, stream, slice_start, (int)S_total, (long)hw,
-                      (const int*)parent, (const unsigned long long*)ctrl, out);
-    return aide_launch_status();
-}
-
-size_t aide_lcc3d_classes_batched_ws_bytes(int64_t nvox_total, int64_t K, int num_classes) {
-    if (nvox_total < 0 || nvox_total > INT32_MAX || K < 0 || K > 65535 || num_classes < 2 || num_classes > MAXC) return 0;
-    return (size_t)(2 * nvox_total) * sizeof(int) + 16 + (size_t)(3 * K * num_classes) * sizeof(unsigned long long);
-}
-
-int aide_keep_largest_cc3d_classes_batched(const long long* v, const long long* slice_start, int64_t K, int64_t S_total,
-                                           int64_t H, int64_t W, int num_classes, unsigned char* out, long long* stats,
-                                           void* ws, hipStream_t stream) {
-    if (num_classes < 2 || num_classes > MAXC || !batch_ok(S_total, H, W, K)) return AIDE_ERR_ARG;
-    const int n = (int)(S_total * H * W), C = num_classes;
-    if (n == 0 || K == 0) {
-        if (!stats || K == 0) return 0;
-        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * K * C) * sizeof(long long), stream);
-    }
-    if (!v || !slice_start || !out || !ws) return AIDE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
-    int* parent = static_cast<int*>(ws);
-    int* area = parent + n;
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
-    Cases g;
-    g.v = v; g.start = slice_start; g.S_total = (int)S_total; g.H = (int)H; g.W = (int)W;
-    g.tw = (int)((W + 15) / 16);
-    const long tiles = (long)g.tw * ((H + 15) / 16), chunks = (H * W + 255) / 256;
-    if (tiles > INT32_MAX) return AIDE_ERR_ARG;
-    const dim3 gt((unsigned)tiles, (unsigned)K), gc((unsigned)chunks, (unsigned)K), block(256);
-    const int hw = (int)(H * W);
-    hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(3 * K * C) * sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return (int)e;
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 29.0 * n, lccb_local_kernel, gt, block, 0, stream, g, parent, area, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_border_kernel, gt, block, 0, stream, g, parent);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_count_kernel, gc, block, 0, stream, slice_start, (int)S_total, hw, parent, area);
-    if (stats)
-        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_classes_kernel<true>, gc, block, 0, stream, g, (const int*)parent,
-                          (const int*)area, C, ctrl);
-    else
-        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_select_classes_kernel<false>, gc, block, 0, stream, g, (const int*)parent,
-                          (const int*)area, C, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lccb_write_classes_kernel, gc, block, 0, stream, g, (const int*)parent, C,
-                      (const unsigned long long*)ctrl, out, stats);
     return aide_launch_status();
 }
 

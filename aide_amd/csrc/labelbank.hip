@@ -10,15 +10,6 @@ namespace {
 
 constexpr int MAX_CASES = 4096;
 
-// slices [s0, s0 + ns) of case k, clamped into [0, S_total] (as in eval3d.hip)
-__device__ __forceinline__ void case_range(const long long* start, int k, int S_total, int& s0, int& ns) {
-    long long a = start[k], b = start[k + 1];
-    a = a < 0 ? 0 : (a > S_total ? S_total : a);
-    b = b < a ? a : (b > S_total ? S_total : b);
-    s0 = (int)a;
-    ns = (int)(b - a);
-}
-
 // a sorts before b: ascending, NaN greatest; equal values (two NaNs included) by the lower case index
 __device__ __forceinline__ bool before(float a, int ia, float b, int ib) {
     const bool na = a != a, nb = b != b;

@@ -86,6 +86,98 @@ def test_batched_filter_case_boundary_and_ties(dev):
     assert got[4:9].sum() == 4 and got[8, 2, 3:7].all()
 
 
+def _winding(h, w, cut):
+    """A ragged batch of three cases with 9, 13 and 1 slices of h x w (the cases of a batch share the plane).  Case k holds
+    one component of value k + 1 that winds through its whole [H,W,S_k] volume (lcc_cases.serpentine in the case's own
+    order: rows along s joined along w, planes of h joined at one corner), so it crosses the 16-wide tile borders in h and w
+    and the 4-deep chunk borders in s.  cut = 2 or 4: the odd plane near H / cut, which holds nothing but the joint of the
+    two halves, is cleared -- in the middle the half that comes first in raster order is the larger one, at a quarter the
+    second one is.  -> [(volume [S_k,H,W], voxels of the larger half or of the whole)]"""
+    import lcc_cases
+    out = []
+    for k, s in enumerate((9, 13, 1)):
+        v = lcc_cases.serpentine(h, w, s, k + 1)
+        keep = int((v != 0).sum())
+        if cut:
+            at = (h // cut) | 1
+            v[at] = 0
+            lo, hi = int((v[:at] != 0).sum()), int((v[at:] != 0).sum())
+            assert lo > 0 and hi > 0 and (lo > hi) == (cut == 2)
+            keep = max(lo, hi)
+        out.append((np.ascontiguousarray(v.transpose(2, 0, 1)), keep))
+    return out
+
+
+@pytest.mark.parametrize('cut', [0, 2, 4], ids=['whole', 'middle', 'quarter'])
+def test_batched_filter_serpentine(dev, cut):
+    """planes of 40 x 70, 33 x 18 and 17 x 31: the binary batched entry against the CPU function (and the per-case device
+    call), the per-class batched entry against the flood fill of lcc_cases -- the whole component is kept, and of a cut one
+    the larger half"""
+    import lcc_cases
+    from aide_amd.inference import keep_largest_batched
+    for h, w in ((40, 70), (33, 18), (17, 31)):
+        vols, keeps = zip(*_winding(h, w, cut))
+        got, start = _check_filter(list(vols), dev)
+        per_class = keep_largest_batched(torch.from_numpy(np.concatenate(vols)).to(dev), torch.from_numpy(start).to(dev),
+                                         num_classes=4).cpu().numpy()
+        for k, v in enumerate(vols):
+            a, b = start[k], start[k + 1]
+            want = lcc_cases.flood_fill(v.transpose(1, 2, 0), 4)[0].transpose(2, 0, 1)
+            assert int((want != 0).sum()) == keeps[k]
+            assert np.array_equal(per_class[a:b], want), (h, w, k, int((per_class[a:b] != 0).sum()), keeps[k])
+            assert np.array_equal(got[a:b], want != 0), (h, w, k, int(got[a:b].sum()), keeps[k])
+            if not cut:
+                assert np.array_equal(per_class[a:b], v)
+
+
+def test_batched_filter_partial_slice_table(dev):
+    """S_total = 7 with slice_start = [0, 3, 5]: slices 5 and 6 belong to no case, and their workspace words are neither read
+    nor written.  The workspace is pre-filled with valid but wrong words, every parent word 0 and every area word 1: an
+    uncovered node that the count stage visited would add its area to root 0, the first voxel of case 0.  Case 0 holds two
+    blobs, one of them at node 0.  With equal areas the blob at node 0 wins the tie with or without such additions; with the
+    blob at node 0 one voxel smaller, a single uncovered node counted into root 0 flips the winner.  Both, for the binary and
+    the per-class entry: slices [0, 5) against the CPU functions and the per-case device calls.  Slices 5 and 6 of `out`
+    are not read."""
+    from aide_amd._lib import lib, check
+    from aide_amd.ops import ptr, stream_ptr
+    from aide_amd.inference import keep_largest_connected_components, keep_largest_per_class
+    S, H, W, K, C = 7, 20, 37, 2, 3
+    n, covered = S * H * W, 5 * H * W
+    start = [0, 3, 5]
+    table = torch.tensor(start, dtype=torch.int64, device=dev)
+    rng = np.random.RandomState(21)
+    for smaller in (0, 1):
+        lab = np.zeros((S, H, W), np.int64)
+        lab[0, 0, 0:6 - smaller] = 1                        # case 0, voxels (h, w, s) = (0, 0 .. 5, 0): the blob of node 0
+        lab[1:3, 17, 30:33] = 1                             # case 0: 6 voxels across the tile border at w = 32
+        lab[3:5] = rng.randint(0, 3, (2, H, W))             # case 1
+        lab[5:] = 1                                         # no case
+        v = torch.from_numpy(lab).to(dev)
+        for classes in (False, True):
+            size = lib.aide_lcc3d_classes_batched_ws_bytes(n, K, C) if classes else lib.aide_lcc3d_batched_ws_bytes(n, K)
+            ws = torch.zeros(size // 4, device=dev, dtype=torch.int32)
+            ws[n:2 * n] = 1
+            out = torch.full((S, H, W), 0xEE, device=dev, dtype=torch.uint8)
+            if classes:
+                check(lib.aide_keep_largest_cc3d_classes_batched(ptr(v), ptr(table), K, S, H, W, C, ptr(out), ptr(None),
+                                                                 ptr(ws), stream_ptr()), 'keep_largest_cc3d_classes_batched')
+            else:
+                check(lib.aide_keep_largest_cc3d_batched(ptr(v), ptr(table), K, S, H, W, ptr(out), ptr(ws), stream_ptr()),
+                      'keep_largest_cc3d_batched')
+            got = out[:5].cpu().numpy()
+            for a, b in zip(start, start[1:]):
+                one, one_dev = lab[a:b].transpose(1, 2, 0), v[a:b].permute(1, 2, 0)
+                if classes:
+                    want, single = keep_largest_per_class(one, C), keep_largest_per_class(one_dev, C)
+                else:
+                    want, single = keep_largest_connected_components(one), keep_largest_connected_components(one_dev)
+                assert np.array_equal(got[a:b].transpose(1, 2, 0), want), (smaller, classes, a, int(got[a:b].sum()))
+                assert np.array_equal(single.cpu().numpy(), want), (smaller, classes, a)
+            assert int(got[:3].sum()) == 6 and bool(got[0, 0, 0]) == (not smaller)
+            words = ws.cpu().numpy()                        # the words of the uncovered nodes are as they were
+            assert not words[covered:n].any() and (words[n + covered:2 * n] == 1).all()
+
+
 def test_batched_filter_full_size(dev):
     rng = np.random.RandomState(9)
     ns = [33, 30, 35, 1, 36, 33]

@@ -100,6 +100,54 @@ def test_same_bytes_whatever_the_workspace_held(dev):
         assert runs[0] == (want.tobytes(), want_stats.tobytes()), name
 
 
+def test_same_bytes_whatever_the_workspace_held_binary_and_batched(dev):
+    """the same through the other entries of the C ABI: a 7 x 20 x 37 volume through the binary filter, and cases of 5, 1
+    and 6 slices at 20 x 37 through the binary and the per-class batched filter, each on a zeroed workspace and on one filled
+    with 0xFF -- identical bytes, and those of the CPU function (binary) and of the flood fill (per class)"""
+    from aide_amd._lib import lib, check
+    from aide_amd.ops import ptr, stream_ptr
+    from aide_amd.inference import keep_largest_connected_components
+    rng = np.random.RandomState(17)
+    c, k, (h, w) = 4, 3, (20, 37)
+    vol = np.where(rng.rand(7, h, w) < 0.55, rng.randint(1, c, (7, h, w)), 0).astype(np.int64)
+    lab = np.where(rng.rand(12, h, w) < 0.55, rng.randint(1, c, (12, h, w)), 0).astype(np.int64)
+    start = [0, 5, 6, 12]
+    cases = [lab[a:b].transpose(1, 2, 0) for a, b in zip(start, start[1:])]
+    want_binary = np.concatenate([keep_largest_connected_components(x).transpose(2, 0, 1) for x in cases])
+    fills = [lcc_cases.flood_fill(x, c) for x in cases]
+    want_classes = np.concatenate([f[0].transpose(2, 0, 1) for f in fills])
+    want_stats = np.stack([f[1] for f in fills])
+    t, tl = torch.from_numpy(vol).to(dev), torch.from_numpy(lab).to(dev)
+    table = torch.tensor(start, dtype=torch.int64, device=dev)
+
+    def single(ws, out, stats):
+        return lib.aide_keep_largest_cc3d(ptr(t), *t.shape, *t.stride(), ptr(out), ptr(ws), stream_ptr())
+
+    def batched(ws, out, stats):
+        return lib.aide_keep_largest_cc3d_batched(ptr(tl), ptr(table), k, *tl.shape, ptr(out), ptr(ws), stream_ptr())
+
+    def classes_batched(ws, out, stats):
+        return lib.aide_keep_largest_cc3d_classes_batched(ptr(tl), ptr(table), k, *tl.shape, c, ptr(out), ptr(stats), ptr(ws),
+                                                          stream_ptr())
+
+    for call, src, size, want, stats_want in (
+            (single, t, lib.aide_lcc3d_ws_bytes(t.numel()), keep_largest_connected_components(vol), None),
+            (batched, tl, lib.aide_lcc3d_batched_ws_bytes(tl.numel(), k), want_binary, None),
+            (classes_batched, tl, lib.aide_lcc3d_classes_batched_ws_bytes(tl.numel(), k, c), want_classes, want_stats)):
+        ws = torch.empty(size, device=dev, dtype=torch.uint8)
+        runs = []
+        for fill in (0x00, 0xFF):
+            ws.fill_(fill)
+            out = torch.full(src.shape, 0xEE, device=dev, dtype=torch.uint8)
+            stats = torch.full((k, c, 3), -1, device=dev, dtype=torch.int64)
+            check(call(ws, out, stats), call.__name__)
+            runs.append((out.cpu().numpy().tobytes(), stats.cpu().numpy().tobytes()))
+        assert runs[0] == runs[1], call.__name__
+        assert runs[0][0] == np.ascontiguousarray(want).astype(np.uint8).tobytes(), call.__name__
+        if stats_want is not None:
+            assert runs[0][1] == stats_want.tobytes(), call.__name__
+
+
 def _ragged(dev):
     """[15, 17, 33] labels 0 .. 4 of four cases with S_k = 1, 5, 0 (empty, in the middle) and 9; the table on the device"""
     rng = np.random.RandomState(3)
