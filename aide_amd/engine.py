@@ -244,6 +244,195 @@ def _wgrad_extra(st):
     return dict(target_wgs=256) if st.get('wg_target') else {}
 
 
+def _readers(ops_, t):
+    """indices of the ops that read any channel of the tensor range t"""
+    return [i for i, o in enumerate(ops_) if o.get('src') is not None and o['src'].root is t.root
+            and o['src'].c0 < t.c0 + t.C and t.c0 < o['src'].c0 + o['src'].C]
+
+
+def _producers(ops_, t):
+    """indices of the conv ops whose output is exactly the tensor range t"""
+    return [i for i, o in enumerate(ops_) if o['kind'] == 'conv' and o['dst'].root is t.root
+            and (o['dst'].c0, o['dst'].C) == (t.c0, t.C)]
+
+
+def _tiling_producers(ops_, t):
+    """indices of the conv ops whose outputs tile the tensor range t exactly (no gap, no overlap, nothing outside); [] when the
+    convs that write into t do not"""
+    prods = [i for i, o in enumerate(ops_) if o['kind'] == 'conv' and o['dst'].root is t.root
+             and t.c0 <= o['dst'].c0 and o['dst'].c0 + o['dst'].C <= t.c0 + t.C]
+    cover = sorted((ops_[i]['dst'].c0, ops_[i]['dst'].c0 + ops_[i]['dst'].C) for i in prods)
+    if not cover or cover[0][0] != t.c0 or cover[-1][1] != t.c0 + t.C or any(a[1] != b[0] for a, b in zip(cover, cover[1:])):
+        return []
+    return prods
+
+
+# what select_fusions decides for one step when no rule fires (the meaning of every key: the step-key table above Plan)
+NO_FUSION = dict(lazy_to=None, tab_c0=None, head_lazy=False, lazy_prod=None, pool_out=None, fwd_fused=False,
+                 src_grad=None, fold_dgrad=False, pool_fuse=None, bwd_fused=False, head_fuse=None, dgrad_fused=False)
+
+
+def select_fusions(graph, convs, cfg, precision, training, groups, n, h, w):
+    """Every decision of a plan that sits on top of the per-layer kernel choice, from the graph, `convs` ({index in graph.ops:
+    what select_conv returned for that conv}) and host-side shape queries of the library alone (no tensor, no device, no
+    stream, no allocation): the bf16 storage of every activation / gradient buffer, the six fusions, and the overwrite /
+    accumulate / zero-fill mode of every backward write.  ->
+        act_bf16, grad_bf16   [per graph.roots entry] the root's activation / gradient buffer is stored as bf16
+        steps                 [per graph.ops entry] a copy of NO_FUSION with the decisions that fired
+    Steps are named by their index in graph.ops; a tensor is [root index in graph.roots, c0, C] (pool_out, pool_fuse) or, for
+    the gaps of src_grad = [accumulate, [[c0, C], ...]], [c0, C] in the root of the step's own src.  The backward-side keys
+    (src_grad and the five after it) are decided only for plans that can run a backward pass: training, groups == 1.  The
+    rules run in this order because each reads what the ones before it decided."""
+    ops_, roots = graph.ops, graph.roots
+    dec = [dict(NO_FUSION) for _ in ops_]
+    rindex = {id(t): i for i, t in enumerate(roots)}
+    zshape = lambda i: (ops_[i]['dst'].C, h >> ops_[i]['dst'].level, w >> ops_[i]['dst'].level)    # C, H, W of conv i's z (and dz)
+    # [root, c0, C] of the channels of `dst` that correspond to the part `part` of `src`
+    sub = lambda dst, part, src: [rindex[id(dst.root)], dst.c0 + part.c0 - src.c0, part.C]
+    # lazy_bn.  Forward-only stacked plans (the no-grad augmentation passes of the co-teaching step,
+    # trainchaos_proposed_30cases1labeled.py:263-281): nothing is kept for a backward pass, so the BatchNorm + ReLU of a
+    # layer whose ONLY reader is an F(4x4) convolution is applied in that convolution's loader (SURVEY 8b
+    # in_prologue{bn_relu}) -- the producer writes its raw output z straight into the reader's input slot with the
+    # statistics from its epilogue, a one-wave-per-channel launch turns them into the reader's per-group (scale, shift)
+    # table, and the normalising pass over the tensor (one read + one write) never runs.  Channels of the reader's input
+    # that are materialised activations (a skip half of a concat buffer) get (1, 0): ReLU of a non-negative value.
+    if training and groups > 1 and cfg.lazy_bn:
+        for i, o in enumerate(ops_):
+            if o['kind'] != 'conv' or not convs[i]['stats_parts']:
+                continue
+            dst = o['dst']
+            readers = _readers(ops_, dst)
+            if len(readers) != 1:
+                continue
+            rd = ops_[readers[0]]
+            src = rd['src']
+            if rd['kind'] != 'conv' or convs[readers[0]]['wino_f'] != 4 or src.C > 1024 or \
+                    not (src.c0 <= dst.c0 and dst.c0 + dst.C <= src.c0 + src.C):
+                continue
+            dec[i]['lazy_to'], dec[i]['tab_c0'] = readers[0], dst.c0 - src.c0      # (no z: the raw output lives in the reader's input slot)
+    # lazy_head.  Training plans: the layer under the 1x1 head (its only reader) with statistics from its conv epilogue never runs
+    # its normalising pass -- a one-wave-per-channel launch turns the statistics into (scale, shift), the head's forward and
+    # weight gradient apply BatchNorm + ReLU while they read z (ops.head1x1_fwd_bn / head1x1_wgrad_bn), and the head's data
+    # gradient is formed inside that layer's BatchNorm backward (fuse_head_bwd): its activation is never stored.
+    if training and groups == 1 and cfg.lazy_head and cfg.fuse_head_bwd:
+        for hi, o in enumerate(ops_):
+            if o['kind'] != 'head':
+                continue
+            prods = _producers(ops_, o['src'])
+            if len(_readers(ops_, o['src'])) != 1 or len(prods) != 1:
+                continue
+            p, c = prods[0], convs[prods[0]]
+            if not c['stats_parts'] or c['z_bf16'] or c['dz_bf16'] or dec[p]['lazy_to'] is not None or \
+                    not lib.aide_bn_one_pass(n, *zshape(p)):
+                continue
+            dec[p]['head_lazy'], dec[hi]['lazy_prod'] = True, p
+    # activation buffers.  bf16 mode stores an activation buffer as bf16 when everything that touches it can: written by
+    # BatchNorm-apply / pooling / up-sampling, read by bf16 convolutions (forward AND weight gradient), pooling,
+    # up-sampling or the head.  For a conv operand that is numerically free (the kernels round it anyway), max-pooling
+    # commutes with the rounding; up-sampling and the head then see rounded inputs (what torch's autocast gives them).
+    narrow = {id(t): precision == 'bf16' and cfg.store_a_bf16 for t in roots}             # (ids of input tensors join it below: never read)
+    for i, o in enumerate(ops_):
+        kind = o['kind']
+        if kind == 'conv':
+            if not (convs[i]['wino_f'] == BF16 and convs[i]['wino_w'] == BF16):
+                narrow[id(o['src'].root)] = False
+        elif kind in ('convT', 'sa'):
+            narrow[id(o['src'].root)] = False
+        if kind == 'sa':
+            narrow[id(o['dst'].root)] = False
+    # pool_fwd.  Training plans: a max-pooling whose source is exactly the output of one or several conv + BN + ReLU layers that
+    # run the one-pass BatchNorm on z as it is (no split-K slabs, no conv-epilogue statistics) is written by those layers'
+    # BatchNorm kernels themselves (ops.bn_train_fwd_pool): the pooling pass and its launch disappear (the first two levels of
+    # the U-Nets).
+    if training and cfg.fuse_pool_fwd and not (groups > 1 and not cfg.grouped_bn):
+        m = n // max(groups, 1)
+        for pi, o in enumerate(ops_):
+            if o['kind'] != 'pool':
+                continue
+            src, dst = o['src'], o['dst']
+            if src.root.is_input or narrow[id(src.root)] or narrow[id(dst.root)]:
+                continue
+            prods = _tiling_producers(ops_, src)
+            if not prods or any(dec[p]['lazy_to'] is not None or convs[p]['z_bf16'] or convs[p]['stats_parts'] or
+                                (convs[p]['plan_f'] >> 8) > 1 or dec[p]['head_lazy'] or
+                                not lib.aide_bn_relu_bwd_pool_supported(m, *zshape(p)) for p in prods):
+                continue
+            for p in prods:
+                dec[p]['pool_out'] = sub(dst, ops_[p]['dst'], src)
+            dec[pi]['fwd_fused'] = True
+    # the gradient of a bf16-stored activation buffer is stored as bf16 too when every conv that reads the buffer also
+    # runs its dgrad on the bf16 kernel (the other writers / readers -- pooling, up-sampling, head, BatchNorm backward --
+    # are storage-generic).  Writers after the first accumulate in fp32 and round once per write (torch autocast's
+    # bf16 activation gradients accumulate the same way).  Gradients of the other activations stay fp32.
+    narrow_grad = {k: v and cfg.store_g_bf16 for k, v in narrow.items()}
+    for i, o in enumerate(ops_):
+        if o['kind'] == 'conv' and not o['src'].root.is_input and convs[i]['wino_d'] != BF16:
+            narrow_grad[id(o['src'].root)] = False
+    out = dict(act_bf16=[narrow[id(t)] for t in roots], grad_bf16=[narrow_grad[id(t)] for t in roots], steps=dec)
+    if not (training and groups == 1):
+        return out
+    # overwrite / accumulate per backward write, in the order the backward pass makes them (_Cover)
+    cover = {id(t): _Cover() for t in roots}
+    for i in reversed(range(len(ops_))):
+        src = ops_[i]['src']
+        if not src.root.is_input:
+            acc, gaps = cover[id(src.root)].write(src.c0, src.c0 + src.C)
+            dec[i]['src_grad'] = [acc, [[a, b - a] for a, b in gaps]]
+
+    def sole_write(i):                   # the step's data gradient overwrites its whole range: nothing before it, no gaps
+        return dec[i]['src_grad'] is not None and not dec[i]['src_grad'][0] and not dec[i]['src_grad'][1]
+    # A split-K data gradient whose ONLY reader is the BatchNorm backward of the conv right before it (conv1 -> conv2 of
+    # a block) stays in its slabs: that kernel sums them (ops.bn_relu_bwd_slabs) -- one launch and one pass less per pair.
+    for i, o in enumerate(ops_):
+        if i == 0 or o['kind'] != 'conv' or not sole_write(i):
+            continue
+        src, c, pc = o['src'], convs[i], convs.get(i - 1)
+        if i - 1 not in _producers(ops_, src) or len(_readers(ops_, src)) != 1:
+            continue                                   # (another reader of (part of) the tensor: its gradient accumulates)
+        if c['wino_d'] not in (2, 4) or (c['plan_d'] >> 8) <= 1 or pc['dz_bf16'] or c['dz_bf16'] or \
+                narrow_grad[id(src.root)] or pc['z_bf16']:
+            continue
+        pch, ph, pw = zshape(i - 1)
+        if not lib.aide_bn_one_pass(n, pch, ph, pw) or (ph * pw) % 4:
+            continue
+        dec[i]['fold_dgrad'] = True
+    # A max-pooling whose source is exactly the output of one or several conv + BN + ReLU layers (the level's skip tensor:
+    # both encoders' second convolutions in the FuseUNet) and whose gradient ACCUMULATES into a skip gradient the decoder has
+    # written: its backward pass disappears -- every such layer's BatchNorm backward routes the pooled gradient to the window
+    # arg-max itself (the activation recomputed from z, bit-identical) while it reads dA (ops.bn_relu_bwd_pool).
+    if cfg.fuse_pool_bwd:
+        for pi, o in enumerate(ops_):
+            sg = dec[pi]['src_grad']
+            if o['kind'] != 'pool' or sg is None or not sg[0] or sg[1]:
+                continue
+            src, dst = o['src'], o['dst']
+            if narrow_grad[id(src.root)] or narrow_grad[id(dst.root)]:
+                continue
+            prods = _tiling_producers(ops_, src)       # ([]: the producers do not tile the pooled channels exactly)
+            if not prods or any(convs[p]['z_bf16'] or convs[p]['dz_bf16'] or
+                                not lib.aide_bn_relu_bwd_pool_supported(n, *zshape(p)) for p in prods):
+                continue
+            for p in prods:
+                dec[p]['pool_fuse'] = sub(dst, ops_[p]['dst'], src)
+            dec[pi]['bwd_fused'] = True
+    # The 1x1 head's data gradient (a write and a read of the widest feature map) is formed inside the BatchNorm backward of the
+    # layer under the head when that layer's activation has no other reader (ops.bn_relu_bwd_head).
+    if cfg.fuse_head_bwd:
+        for hi, o in enumerate(ops_):
+            if o['kind'] != 'head' or not sole_write(hi):
+                continue
+            prods = _producers(ops_, o['src'])
+            if len(_readers(ops_, o['src'])) != 1 or len(prods) != 1:
+                continue
+            p, c = prods[0], convs[prods[0]]
+            zc, zh, zw = zshape(p)
+            if c['z_bf16'] or c['dz_bf16'] or dec[p]['pool_fuse'] is not None or \
+                    not lib.aide_bn_one_pass(n, zc, zh, zw) or (zh * zw) % 4:
+                continue
+            dec[p]['head_fuse'], dec[hi]['dgrad_fused'] = hi, True
+    return out
+
+
 def _pack_slot(mode, direction):
     """step key of a conv's filter pack of one direction ('f' | 'd'): 'wf' / 'wd' direct kernel, 'uf' / 'ud' the others"""
     return ('u' if mode else 'w') + direction
@@ -301,6 +490,37 @@ class _Cover(object):
         self.iv = out
 
 
+# The keys of a plan's step dicts (plan.steps[i]: the graph op's own keys -- kind, src, dst, conv, bn, mod, lane, lane_split --
+# plus these).  "fusions": decided by select_fusions, written by Plan.__init__ with indices resolved to step dicts and
+# [root, c0, C] to GTensor slices; "conv": select_conv's result as it is; "init" / "bwd": allocated by Plan.__init__ /
+# _prepare_backward.
+#
+#   key                          set by     read by                      meaning
+#   wino_f wino_d wino_w         conv       _forward_op _backward_op     kernel family per direction
+#     plan_f plan_d                         _pack_filters                variant | splitk << 8 of the forward / dgrad launch
+#     wg_target wg_bytes                    _backward_op _prepare_backward   weight gradient: workgroup target, workspace bytes
+#     stats_parts fold                      _forward_op _bn_apply        conv-epilogue statistics partials; eval BatchNorm fold
+#     z_bf16 dz_bf16                        __init__ _prepare_backward   storage of z / dz
+#   wf wd uf ud                  init       _pack_filters, executors     filter packs (_pack_slot); flops, pack_key beside them
+#   z                            init       executors                    conv output; None under lazy_to
+#   mean rstd scale shift fbias  init       executors                    BatchNorm per-channel vectors
+#   stats                        init       _forward_op _bn_apply        the statistics partials (None: stats_parts == 0)
+#   t1 t2 t3 t4 gate stat        init       executors ('sa')             spatial-attention intermediates
+#   ev_b                         init       _forward_impl                split pooling: lane 1's half is pooled
+#   lazy_to, tab_c0              fusions    _forward_op                  reader step whose loader applies this layer's BatchNorm
+#                                                                        + ReLU; first channel of its rows in the reader's in_tab
+#   in_tab                       init       _forward_op                  that reader's [groups, Cin, 2] (scale, shift) table
+#   head_lazy, head_tab          fusions    _forward_op, tests           the head applies this layer's BatchNorm + ReLU; its table
+#   lazy_prod                    fusions    _forward_op _backward_op     head: the head_lazy step under it
+#   pool_out                     fusions    _bn_apply                    pooled slice this layer's BatchNorm forward also writes
+#   fwd_fused                    fusions    _forward_op _forward_impl, tests   pool: written by its producers (pool_out)
+#   src_grad                     fusions    _backward_op                 None (network input) | dict(accumulate, gaps to zero-fill)
+#   fold_dgrad                   fusions    _backward_op                 split-K dgrad slabs summed by the BatchNorm backward before
+#   pool_fuse                    fusions    _backward_op                 pooled-gradient slice this layer's BatchNorm backward routes
+#   bwd_fused                    fusions    _backward_op, tests          pool: its backward runs in its producers (pool_fuse)
+#   head_fuse                    fusions    _backward_op, tests          head step whose data gradient this BatchNorm backward forms
+#   dgrad_fused                  fusions    _backward_op                 head: its data gradient is formed below it (head_fuse)
+#   dz wg_off wg_ws ev           bwd        _backward_op                 dz buffer, weight-gradient slab region, hand-over event
 class Plan(object):
     def __init__(self, graph, params, n, h, w, device, training, precision='fp32', groups=1, shared=None, cfg=None):
         self.g, self.N, self.H, self.W, self.dev, self.training = graph, n, h, w, device, training
@@ -315,7 +535,6 @@ class Plan(object):
         # and updates its running statistics per group, in order -- the semantics of `groups` sequential forwards
         self.groups = groups
         assert n % groups == 0
-        bf16 = precision == 'bf16'
         self.pindex = {id(p): i for i, p in enumerate(params)}
         f32 = dict(device=device, dtype=torch.float32)
         forward_only = (groups > 1 or not training) and cfg.shared_packs   # no backward pass will ever run on this plan: no dgrad-direction packs
@@ -329,7 +548,8 @@ class Plan(object):
         self.act = {}
         self.grad = {}
         self.steps = []
-        max_dz = max_wg = max_bnc = max_sk = 0
+        convs = {}                       # index in graph.ops -> what select_conv decided for that conv
+        max_wg = max_bnc = max_sk = 0
         stem_only = True                 # every op so far is a stem conv without a data gradient (select_conv)
         for op in graph.ops:
             st = dict(op)
@@ -337,10 +557,8 @@ class Plan(object):
                 conv, src, dst = op['conv'], op['src'], op['dst']
                 hh, ww = h >> dst.level, w >> dst.level
                 cout = dst.C
-                st['z'] = torch.empty(n, cout, hh, ww, **f32)
                 for k in ('mean', 'rstd', 'scale', 'shift', 'fbias'):
                     st[k] = torch.empty(cout, **f32)
-                max_dz = max(max_dz, n * cout * hh * ww)
                 max_bnc = max(max_bnc, cout)
                 if op['kind'] == 'conv':
                     cin = src.C
@@ -348,6 +566,7 @@ class Plan(object):
                     sel = select_conv(cfg, precision, training, groups, n, cin, cout, hh, ww, need_dg, stem_only)
                     max_sk = max(max_sk, sel.pop('sk_f'), sel.pop('sk_d'))
                     st.update(sel)
+                    convs[len(self.steps)] = sel
                     st['wf'] = st['wd'] = st['uf'] = st['ud'] = None
                     for direction, ci, co in [('f', cin, cout)] + ([('d', cout, cin)] if need_dg else []):
                         fam = FAMILIES[st['wino_' + direction]]
@@ -357,8 +576,6 @@ class Plan(object):
                     st['stats'] = torch.empty(cout * st['stats_parts'] * 2, **f32) if st['stats_parts'] else None
                     st['pack_key'] = None
                     st['flops'] = 2.0 * n * hh * ww * cout * cin * 9      # algorithmic, per launch
-                    if st['z_bf16']:
-                        st['z'] = torch.empty(n, cout, hh, ww, device=device, dtype=torch.bfloat16)
                 else:
                     cin = src.C
                     st['wg_bytes'] = lib.aide_convT2x2_wgrad_ws_bytes(n, cin, cout, h >> src.level, w >> src.level)
@@ -378,35 +595,30 @@ class Plan(object):
                 st['stat'] = torch.empty(2, **f32)
             stem_only = stem_only and op['kind'] == 'conv' and op['src'].root.is_input
             self.steps.append(st)
-        self._plan_lazy_bn()
-        self._plan_lazy_head()
-        # activation buffers.  bf16 mode stores an activation buffer as bf16 when everything that touches it can: written by
-        # BatchNorm-apply / pooling / up-sampling, read by bf16 convolutions (forward AND weight gradient), pooling,
-        # up-sampling or the head.  For a conv operand that is numerically free (the kernels round it anyway), max-pooling
-        # commutes with the rounding; up-sampling and the head then see rounded inputs (what torch.autocast gives them).
-        # Gradients of activations stay fp32.
-        narrow = {id(t): bf16 and cfg.store_a_bf16 for t in graph.roots}
-        for st in self.steps:
-            kind = st['kind']
-            if kind == 'conv':
-                if not (st['wino_f'] == BF16 and st['wino_w'] == BF16):
-                    narrow[id(st['src'].root)] = False
-            elif kind in ('convT', 'sa'):
-                narrow[id(st['src'].root)] = False
-            if kind == 'sa':
-                narrow[id(st['dst'].root)] = False
-        for t in graph.roots:
-            dt = torch.bfloat16 if narrow.get(id(t)) else torch.float32
-            self.act[id(t)] = torch.empty(n, t.C, h >> t.level, w >> t.level, device=device, dtype=dt)
-        self._plan_pool_fwd()
-        # the gradient of a bf16-stored activation buffer is stored as bf16 too when every conv that reads the buffer also
-        # runs its dgrad on the bf16 kernel (the other writers / readers -- pooling, up-sampling, head, BatchNorm backward --
-        # are storage-generic).  Writers after the first accumulate in fp32 and round once per write (torch.autocast's
-        # bf16 activation gradients accumulate the same way).
-        self.narrow_grad = {k: v and cfg.store_g_bf16 for k, v in narrow.items()}
-        for st in self.steps:
-            if st['kind'] == 'conv' and not st['src'].root.is_input and st['wino_d'] != BF16:
-                self.narrow_grad[id(st['src'].root)] = False
+        # every decision on top of the per-layer kernel choice is select_fusions'; from here on: allocation, and indices
+        # resolved to step dicts and tensor slices under the step keys the executors read (the table above this class)
+        fus = select_fusions(graph, convs, cfg, precision, training, groups, n, h, w)
+        step = lambda i: None if i is None else self.steps[i]
+        tensor = lambda r: None if r is None else graph.roots[r[0]].slice(r[1], r[2])
+        for st, d in zip(self.steps, fus['steps']):
+            sg = d['src_grad']
+            st.update(d, lazy_to=step(d['lazy_to']), lazy_prod=step(d['lazy_prod']), head_fuse=step(d['head_fuse']),
+                      pool_out=tensor(d['pool_out']), pool_fuse=tensor(d['pool_fuse']),
+                      src_grad=sg and dict(accumulate=sg[0], gaps=[st['src'].root.slice(*g) for g in sg[1]]))
+            rd, dst = st['lazy_to'], st.get('dst')
+            if st['kind'] in ('conv', 'convT'):          # (lazy_to: no z, the raw output lives in the reader's input slot)
+                st['z'] = None if rd is not None else torch.empty(
+                    n, dst.C, h >> dst.level, w >> dst.level, device=device, dtype=torch.bfloat16 if st.get('z_bf16') else torch.float32)
+            if st['head_lazy']:
+                st['head_tab'] = torch.zeros(1, dst.C, 2, **f32)
+            if rd is not None and rd.get('in_tab') is None:
+                rd['in_tab'] = torch.zeros(groups, rd['src'].C, 2, **f32)
+                rd['in_tab'][:, :, 0] = 1.0
+        self.lazy_bn = sum(1 for st in self.steps if st['lazy_to'] is not None)
+        for t, narrow in zip(graph.roots, fus['act_bf16']):
+            self.act[id(t)] = torch.empty(n, t.C, h >> t.level, w >> t.level, device=device,
+                                          dtype=torch.bfloat16 if narrow else torch.float32)
+        self.narrow_grad = {id(t): narrow for t, narrow in zip(graph.roots, fus['grad_bf16'])}
         self.bn_ws = ops.bn_ws(max(max_bnc, 1), device)
         self.sk_ws = torch.empty(max(max_sk // 4, 1), **f32)
         self.lane_b = None               # second forward stream + its own BatchNorm / split-K workspaces (lane-1 chains)
@@ -419,7 +631,7 @@ class Plan(object):
             for st in self.steps:        # one event per split pooling op: "lane 1's half of this level is pooled"
                 if st['kind'] == 'pool' and st.get('lane_split'):
                     st['ev_b'] = ops.new_event()
-        self._max_dz, self._max_wg = max_dz, max_wg
+        self._max_wg = max_wg
         self.wg_ws = self.wg_queue = self._wq_active = None
         self._bwd_ready = False
         self.profiler = None             # set by Engine (bench.py's per-kernel HIP-event timing)
@@ -439,96 +651,6 @@ class Plan(object):
         self.serial = 0                  # forwards run on this plan; _NetFunction.backward checks it still owns the buffers
         self.key = None
 
-    def _plan_lazy_bn(self):
-        """Forward-only stacked plans (the no-grad augmentation passes of the co-teaching step,
-        trainchaos_proposed_30cases1labeled.py:263-281): nothing is kept for a backward pass, so the BatchNorm + ReLU of a
-        layer whose ONLY reader is an F(4x4) convolution is applied in that convolution's loader (SURVEY 8b
-        in_prologue{bn_relu}) -- the producer writes its raw output z straight into the reader's input slot with the
-        statistics from its epilogue, a one-wave-per-channel launch turns them into the reader's per-group (scale, shift)
-        table, and the normalising pass over the tensor (one read + one write) never runs.  Channels of the reader's input
-        that are materialised activations (a skip half of a concat buffer) get (1, 0): ReLU of a non-negative value."""
-        self.lazy_bn = 0
-        if not (self.training and self.groups > 1) or not self.cfg.lazy_bn:
-            return
-        for st in self.steps:
-            if st['kind'] != 'conv' or st.get('stats') is None:
-                continue
-            dst = st['dst']
-            readers = [o for o in self.steps if o.get('src') is not None and o['src'].root is dst.root
-                       and o['src'].c0 < dst.c0 + dst.C and dst.c0 < o['src'].c0 + o['src'].C]
-            if len(readers) != 1:
-                continue
-            rd = readers[0]
-            src = rd['src']
-            if rd['kind'] != 'conv' or rd['wino_f'] != 4 or src.C > 1024 or not (src.c0 <= dst.c0 and dst.c0 + dst.C <= src.c0 + src.C):
-                continue
-            if rd.get('in_tab') is None:
-                tab = torch.zeros(self.groups, src.C, 2, device=self.dev, dtype=torch.float32)
-                tab[:, :, 0] = 1.0
-                rd['in_tab'] = tab
-            st['lazy_to'], st['tab_c0'] = rd, dst.c0 - src.c0
-            st['z'] = None                 # the raw output lives in the reader's input slot
-            self.lazy_bn += 1
-
-    def _plan_lazy_head(self):
-        """Training plans: the layer under the 1x1 head (its only reader) with statistics from its conv epilogue never runs its
-        normalising pass -- a one-wave-per-channel launch turns the statistics into (scale, shift), the head's forward and weight
-        gradient apply BatchNorm + ReLU while they read z (ops.head1x1_fwd_bn / head1x1_wgrad_bn), and the head's data gradient is
-        formed inside that layer's BatchNorm backward (fuse_head_bwd): its activation is never stored."""
-        if not (self.training and self.groups == 1 and self.cfg.lazy_head and self.cfg.fuse_head_bwd):
-            return
-        for hst in self.steps:
-            if hst['kind'] != 'head':
-                continue
-            src = hst['src']
-            readers = [o for o in self.steps if o.get('src') is not None and o['src'].root is src.root
-                       and o['src'].c0 < src.c0 + src.C and src.c0 < o['src'].c0 + o['src'].C]
-            prods = [o for o in self.steps if o['kind'] == 'conv' and o['dst'].root is src.root
-                     and (o['dst'].c0, o['dst'].C) == (src.c0, src.C)]
-            if len(readers) != 1 or len(prods) != 1:
-                continue
-            o = prods[0]
-            zn, zc, zh, zw = o['z'].shape
-            if o.get('stats') is None or o['z'].dtype != torch.float32 or o.get('dz_bf16') or o.get('lazy_to') is not None or \
-                    not lib.aide_bn_one_pass(zn, zc, zh, zw):
-                continue
-            o['head_lazy'] = True
-            o['head_tab'] = torch.zeros(1, zc, 2, device=self.dev, dtype=torch.float32)
-            hst['lazy_prod'] = o
-
-    def _plan_pool_fwd(self):
-        """Training plans: a max-pooling whose source is exactly the output of one or several conv + BN + ReLU layers that run the
-        one-pass BatchNorm on z as it is (no split-K slabs, no conv-epilogue statistics) is written by those layers' BatchNorm
-        kernels themselves (ops.bn_train_fwd_pool): the pooling pass and its launch disappear (the first two levels of the U-Nets)."""
-        if not (self.training and self.cfg.fuse_pool_fwd) or (self.groups > 1 and not self.cfg.grouped_bn):
-            return
-        m = self.N // max(self.groups, 1)
-        for pst in self.steps:
-            if pst['kind'] != 'pool':
-                continue
-            src, dst = pst['src'], pst['dst']
-            if src.root.is_input or self.act[id(src.root)].dtype != torch.float32 or self.act[id(dst.root)].dtype != torch.float32:
-                continue
-            prods = [o for o in self.steps if o['kind'] == 'conv' and o['dst'].root is src.root
-                     and src.c0 <= o['dst'].c0 and o['dst'].c0 + o['dst'].C <= src.c0 + src.C]
-            cover = sorted((o['dst'].c0, o['dst'].c0 + o['dst'].C) for o in prods)
-            if not cover or cover[0][0] != src.c0 or cover[-1][1] != src.c0 + src.C or any(a[1] != b[0] for a, b in zip(cover, cover[1:])):
-                continue
-            ok = True
-            for o in prods:
-                if o.get('z') is None or o['z'].dtype != torch.float32:
-                    ok = False
-                    break
-                zn, zc, zh, zw = o['z'].shape
-                if o.get('stats') is not None or (o['plan_f'] >> 8) > 1 or o.get('lazy_to') is not None or o.get('head_lazy') or \
-                        not lib.aide_bn_relu_bwd_pool_supported(m, zc, zh, zw):
-                    ok = False
-            if not ok:
-                continue
-            for o in prods:
-                o['pool_out'] = dst.slice(o['dst'].c0 - src.c0, o['dst'].C)
-            pst['fwd_fused'] = True
-
     # ------------------------------------------------------------------ helpers
     def view(self, t, inputs=None):
         if t.root.is_input:
@@ -542,29 +664,29 @@ class Plan(object):
         return buf if (t.c0 == 0 and t.C == t.root.C) else buf[:, t.c0:t.c0 + t.C]
 
     def _prepare_backward(self):
-        """Allocate gradient buffers and resolve overwrite/accumulate per backward write."""
+        """Allocate what only a backward pass needs, at the first one: gradient buffers, dz, weight-gradient slabs, the reduce
+        queue and the events.  (What the pass launches was decided with the plan: select_fusions.)"""
+        assert self.training and self.groups == 1, 'select_fusions decided no backward side for this plan'
+        if any(st['kind'] == 'convT' and st['src_grad'] is not None and st['src_grad']['accumulate'] for st in self.steps):
+            raise NotImplementedError('ConvTranspose input with several consumers')
         f32 = dict(device=self.dev, dtype=torch.float32)
         n, h, w = self.N, self.H, self.W
         for t in self.g.roots:
             dt = torch.bfloat16 if self.narrow_grad.get(id(t)) else torch.float32
             self.grad[id(t)] = torch.empty(n, t.C, h >> t.level, w >> t.level, device=self.dev, dtype=dt)
         # one dz buffer per conv: the weight-gradient kernels run on a side stream and may still be
-        # reading dz of layer L while the main stream already produces dz of layer L-1
-        for st in self.steps:
-            if st['kind'] in ('conv', 'convT'):
-                st['dz'] = torch.empty(st['z'].shape, device=self.dev,
-                                       dtype=torch.bfloat16 if st.get('dz_bf16') else torch.float32)
-        # weight-gradient slab workspaces: one region per layer, so that the per-split partial results of every layer
+        # reading dz of layer L while the main stream already produces dz of layer L-1.
+        # Weight-gradient slab workspaces: one region per layer, so that the per-split partial results of every layer
         # survive until the ONE batched reduce launch at the end of the backward pass (aide_wgrad_reduce_flush)
-        off = 0
-        for st in self.steps:
-            if st['kind'] in ('conv', 'convT'):
-                st['wg_off'] = off
-                off += (st['wg_bytes'] // 4 + 63) // 64 * 64
+        layers, off = [st for st in self.steps if st['kind'] in ('conv', 'convT')], 0
+        for st in layers:
+            st['dz'] = torch.empty(st['z'].shape, device=self.dev, dtype=torch.bfloat16 if st.get('dz_bf16') else torch.float32)
+            st['ev'] = ops.new_event()         # main -> side fork of this layer's weight gradient
+            st['wg_off'] = off
+            off += (st['wg_bytes'] // 4 + 63) // 64 * 64
         self.wg_ws = torch.empty(max(off, 1), **f32)
-        for st in self.steps:
-            if st['kind'] in ('conv', 'convT'):
-                st['wg_ws'] = self.wg_ws[st['wg_off']:st['wg_off'] + max(st['wg_bytes'] // 4, 1)]
+        for st in layers:
+            st['wg_ws'] = self.wg_ws[st['wg_off']:st['wg_off'] + max(st['wg_bytes'] // 4, 1)]
         self.head_ws = torch.empty(max(self._max_wg // 4, 1), **f32)
         self.wg_queue = ops.new_wgrad_queue()     # pending slab reduces of a backward pass (batched launches)
         sa = [st for st in self.steps if st['kind'] == 'sa']
@@ -572,98 +694,7 @@ class Plan(object):
             big = max(st['t1'].numel() for st in sa)
             self.sa_da, self.sa_db = torch.empty(big, **f32), torch.empty(big, **f32)
             self.sa_ws = torch.empty(max(st['gate'].numel() for st in sa) * 2 + 8, **f32)
-        if self.side is None:
-            self.side = _side_stream(self.dev)
         self.ev_fork, self.ev_join = ops.new_event(), ops.new_event()
-        for st in self.steps:
-            if st['kind'] in ('conv', 'convT'):
-                st['ev'] = ops.new_event()     # main -> side fork of this layer's weight gradient
-        cover = {id(t): _Cover() for t in self.g.roots}
-        for st in reversed(self.steps):
-            src = st['src']
-            if src.root.is_input:
-                st['src_grad'] = None
-                continue
-            acc, gaps = cover[id(src.root)].write(src.c0, src.c0 + src.C)
-            st['src_grad'] = dict(accumulate=acc, gaps=[src.root.slice(a, b - a) for a, b in gaps])
-            if st['kind'] == 'convT' and acc:
-                raise NotImplementedError('ConvTranspose input with several consumers')
-        # A split-K data gradient whose ONLY reader is the BatchNorm backward of the conv right before it (conv1 -> conv2 of
-        # a block) stays in its slabs: that kernel sums them (ops.bn_relu_bwd_slabs) -- one launch and one pass less per pair.
-        for i, st in enumerate(self.steps):
-            st['fold_dgrad'] = False
-            sg = st.get('src_grad')
-            if i == 0 or st['kind'] != 'conv' or sg is None or sg['accumulate'] or sg['gaps']:
-                continue
-            prod = self.steps[i - 1]
-            src, dst = st['src'], prod.get('dst')
-            if prod['kind'] != 'conv' or dst is None or dst.root is not src.root or (dst.c0, dst.C) != (src.c0, src.C):
-                continue
-            if sum(1 for o in self.steps if o.get('src') is not None and o['src'].root is src.root
-                   and o['src'].c0 < src.c0 + src.C and src.c0 < o['src'].c0 + o['src'].C) != 1:
-                continue                                   # another reader of (part of) the tensor: its gradient accumulates
-            if st['wino_d'] not in (2, 4) or (st['plan_d'] >> 8) <= 1 or prod.get('dz_bf16') or st.get('dz_bf16'):
-                continue
-            if self.grad[id(src.root)].dtype != torch.float32 or prod['z'].dtype != torch.float32:
-                continue
-            pn, pc, ph, pw = prod['z'].shape
-            if not lib.aide_bn_one_pass(pn, pc, ph, pw) or (ph * pw) % 4:
-                continue
-            st['fold_dgrad'] = True
-        # A max-pooling whose source is exactly the output of one or several conv + BN + ReLU layers (the level's skip tensor:
-        # both encoders' second convolutions in the FuseUNet) and whose gradient ACCUMULATES into a skip gradient the decoder has
-        # written: its backward pass disappears -- every such layer's BatchNorm backward routes the pooled gradient to the window
-        # arg-max itself (the activation recomputed from z, bit-identical) while it reads dA (ops.bn_relu_bwd_pool).
-        for st in self.steps:
-            st.pop('pool_fuse', None)
-            st.pop('bwd_fused', None)
-            st.pop('head_fuse', None)
-            st.pop('dgrad_fused', None)
-        if self.cfg.fuse_pool_bwd:
-            for pst in self.steps:
-                sg = pst.get('src_grad')
-                if pst['kind'] != 'pool' or sg is None or not sg['accumulate'] or sg['gaps']:
-                    continue
-                src, dst = pst['src'], pst['dst']
-                if self.grad[id(src.root)].dtype != torch.float32 or self.grad[id(dst.root)].dtype != torch.float32:
-                    continue
-                prods = [o for o in self.steps if o['kind'] == 'conv' and o['dst'].root is src.root
-                         and src.c0 <= o['dst'].c0 and o['dst'].c0 + o['dst'].C <= src.c0 + src.C]
-                cover = sorted((o['dst'].c0, o['dst'].c0 + o['dst'].C) for o in prods)
-                if not cover or cover[0][0] != src.c0 or cover[-1][1] != src.c0 + src.C or \
-                        any(a[1] != b[0] for a, b in zip(cover, cover[1:])):
-                    continue                                   # the producers do not tile the pooled channels exactly
-                ok = True
-                for o in prods:
-                    zn, zc, zh, zw = o['z'].shape
-                    if o['z'].dtype != torch.float32 or o.get('dz_bf16') or not lib.aide_bn_relu_bwd_pool_supported(zn, zc, zh, zw):
-                        ok = False
-                if not ok:
-                    continue
-                for o in prods:
-                    o['pool_fuse'] = dst.slice(o['dst'].c0 - src.c0, o['dst'].C)
-                pst['bwd_fused'] = True
-        # The 1x1 head's data gradient (a write and a read of the widest feature map) is formed inside the BatchNorm backward of the
-        # layer under the head when that layer's activation has no other reader (ops.bn_relu_bwd_head).
-        if self.cfg.fuse_head_bwd:
-            for hst in self.steps:
-                sg = hst.get('src_grad')
-                if hst['kind'] != 'head' or sg is None or sg['accumulate'] or sg['gaps']:
-                    continue
-                src = hst['src']
-                readers = [o for o in self.steps if o.get('src') is not None and o['src'].root is src.root
-                           and o['src'].c0 < src.c0 + src.C and src.c0 < o['src'].c0 + o['src'].C]
-                prods = [o for o in self.steps if o['kind'] == 'conv' and o['dst'].root is src.root
-                         and (o['dst'].c0, o['dst'].C) == (src.c0, src.C)]
-                if len(readers) != 1 or len(prods) != 1:
-                    continue
-                o = prods[0]
-                zn, zc, zh, zw = o['z'].shape
-                if o['z'].dtype != torch.float32 or o.get('dz_bf16') or o.get('pool_fuse') is not None or \
-                        not lib.aide_bn_one_pass(zn, zc, zh, zw) or (zh * zw) % 4:
-                    continue
-                o['head_fuse'] = hst
-                hst['dgrad_fused'] = True
         self._bwd_ready = True
 
     # ------------------------------------------------------------------ forward
@@ -1204,9 +1235,9 @@ class Plan(object):
                 # optimizer: side stream, so that the dependent chain starts with the data gradient alone
                 with ops.use_stream(side):
                     wgrad_only()
-                if dsrc is not None:
-                    ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc, None, None,
-                                    ws=self.head_ws)
+                if dsrc is not None:        # (lazy_prod: the activation slot was never written; x only feeds dw, None here)
+                    ops.head1x1_bwd(dlogits, lp['z'] if lp is not None else self.view(st['src'], inputs),
+                                    conv.weight.view(k, -1), dsrc, None, None, ws=self.head_ws)
             elif lp is not None:
                 wgrad_only()
                 if dsrc is not None:
@@ -1304,8 +1335,6 @@ class Plan(object):
             if sg is not None:
                 ops.upsample2x_bwd(self.gview(st['dst']), self.gview(st['src']),
                                    accumulate=sg['accumulate'])
-
-
 
 
 def _has_param_hooks(params):

@@ -1,7 +1,8 @@
-"""The launch sequences of four fuseunet plans against fixture g27 (tools/gen_golden_launch_trace.py, recorded on the commit the
-fixture names): entry-point names, their order and every scalar argument of the forward and backward launch tapes, and the
-(n, total_blocks) of every kernel family's filter-pack tables.  Equality, no tolerance: host-side refactors of the engine must
-not move a launch."""
+"""The launch sequences of four fuseunet plans at 128x128 against fixture g27, and of the training and the stacked plan at 256x256
+-- where the conv-epilogue statistics and with them the lazy BatchNorm paths fire -- against g29 (tools/gen_golden_launch_trace.py,
+recorded on the commit each fixture names): entry-point names, their order and every scalar argument of the forward and backward
+launch tapes, and the (n, total_blocks) of every kernel family's filter-pack tables.  Equality, no tolerance: host-side
+refactors of the engine must not move a launch."""
 import json
 import os
 import sys
@@ -12,14 +13,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'g27_launch_trace.json')
 
 
+FIXTURE_256 = os.path.join(ROOT, 'tests', 'golden', 'g29_launch_trace_256.json')
+
+
 @pytest.fixture(scope='module')
 def fixture():
-    with open(FIXTURE) as f:
-        return json.load(f)
+    plans = {}
+    for path in (FIXTURE, FIXTURE_256):
+        with open(path) as f:
+            plans.update(json.load(f)['plans'])
+    return dict(plans=plans)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['train_fp32', 'train_bf16', 'eval_fp32', 'stacked_fp32'])
+@pytest.mark.parametrize('name', ['train_fp32', 'train_bf16', 'eval_fp32', 'stacked_fp32',
+                                  'train_fp32_256', 'stacked_fp32_256'])
 def test_launch_trace_matches_fixture(dev, fixture, name):
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     try:
@@ -27,7 +35,8 @@ def test_launch_trace_matches_fixture(dev, fixture, name):
     finally:
         sys.path.pop(0)
     want = fixture['plans'][name]
-    got = json.loads(json.dumps(G.trace(*(G.PLANS[name] + (dev,)))))       # (tuples -> lists, as the fixture went through JSON)
+    args = G.PLANS[name] if name in G.PLANS else G.PLANS_256[name]
+    got = json.loads(json.dumps(G.trace(*(args + (dev,)))))       # (tuples -> lists, as the fixture went through JSON)
     assert sorted(got) == sorted(want)
     assert got['packs'] == want['packs']
     for k in ('forward', 'backward'):

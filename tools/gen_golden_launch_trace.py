@@ -1,6 +1,7 @@
-"""Writes tests/golden/g27_launch_trace.json: the launch sequences of four fuseunet plans, as their launch tapes recorded them.
+"""Writes tests/golden/g27_launch_trace.json: the launch sequences of four fuseunet plans, as their launch tapes recorded them,
+or (--set 256) tests/golden/g29_launch_trace_256.json: those of the training and the stacked plan at 256x256.
 
-    python tools/gen_golden_launch_trace.py --commit $(git rev-parse HEAD)
+    python tools/gen_golden_launch_trace.py --commit $(git rev-parse HEAD) [--set 256]
 
 Needs a GPU.  Every plan of PLANS runs one forward and, where it trains ungrouped, one backward through CEMDiceLoss, with
 replay on and fixed seeds; the recorded tapes (plan._tape_f / plan._tape_b) are dumped as [entry-point name, [every
@@ -10,7 +11,10 @@ and of the side-stream launch (plan._pack_tabs; the pack launches run before the
 generated on the commit it names; tests/test_gpu_launch_trace.py regenerates the dumps with trace_all() and wants them equal.
 
 The traces must hold every 3x3-conv LAUNCH entry point profiles/r05_abi_coverage.md lists as reached (entries that take a
-stream; the pack launches are covered by `packs`): a plan that misses one at 128x128 would move to 256x256."""
+stream; the pack launches are covered by `packs`): a plan that misses one at 128x128 would move to 256x256.
+
+The 256x256 set exists for the lazy BatchNorm paths: conv-epilogue statistics, their precondition, first appear at that size for
+these batches.  Its traces must hold aide_bn_finalize_groups, the training trace also the head's BatchNorm-applying launches."""
 import argparse
 import ctypes
 import json
@@ -29,6 +33,9 @@ OUT = os.path.join(ROOT, 'tests', 'golden', 'g27_launch_trace.json')
 # name -> (n, size, training, precision, groups)
 PLANS = dict(train_fp32=(2, 128, True, 'fp32', 1), train_bf16=(2, 128, True, 'bf16', 1), eval_fp32=(1, 128, False, 'fp32', 1),
              stacked_fp32=(6, 128, True, 'fp32', 3))
+PLANS_256 = dict(train_fp32_256=(2, 256, True, 'fp32', 1), stacked_fp32_256=(6, 256, True, 'fp32', 3))
+SETS = {'128': (PLANS, OUT, 'every plan at 128x128'),
+        '256': (PLANS_256, os.path.join(ROOT, 'tests', 'golden', 'g29_launch_trace_256.json'), 'every plan at 256x256')}
 PACK_MODES = (0, 2, 4, 16)           # order of the per-family tables where a tree keeps them as a tuple
 
 
@@ -78,8 +85,12 @@ def trace(n, size, training, precision, groups, dev):
     return out
 
 
-def trace_all(dev):
-    return {name: trace(*(args + (dev,))) for name, args in PLANS.items()}
+def trace_all(dev, plans=PLANS):
+    return {name: trace(*(args + (dev,))) for name, args in plans.items()}
+
+
+def names(tr):
+    return {c[0] for k in ('forward', 'backward') for c in tr.get(k, ())}
 
 
 def reached_conv_launches():
@@ -94,14 +105,22 @@ def reached_conv_launches():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--commit', required=True, help='hash of the commit this tree is (stated in the fixture)')
-    ap.add_argument('--out', default=OUT)
+    ap.add_argument('--set', default='128', choices=sorted(SETS), help='which plan set (and fixture) to write')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    traces = trace_all(torch.device('cuda:0'))
-    seen = {c[0] for tr in traces.values() for k in ('forward', 'backward') for c in tr.get(k, ())}
-    missing = [nm for nm in reached_conv_launches() if nm not in seen]
-    assert not missing, 'conv launch entry points no trace holds: %s' % missing
+    plans, out, sizes = SETS[args.set]
+    args.out = args.out or out
+    traces = trace_all(torch.device('cuda:0'), plans)
+    if args.set == '128':
+        seen = set().union(*(names(tr) for tr in traces.values()))
+        missing = [nm for nm in reached_conv_launches() if nm not in seen]
+        assert not missing, 'conv launch entry points no trace holds: %s' % missing
+    else:                                                             # the lazy paths fire
+        for name, tr in traces.items():
+            assert 'aide_bn_finalize_groups' in names(tr), name
+        assert names(traces['train_fp32_256']) >= {'aide_head1x1_fwd_bn', 'aide_head1x1_wgrad_bn'}
     with open(args.out, 'w') as f:
-        f.write('{"commit": %s,\n "sizes": "every plan at 128x128",\n "plans": {\n' % json.dumps(args.commit))
+        f.write('{"commit": %s,\n "sizes": %s,\n "plans": {\n' % (json.dumps(args.commit), json.dumps(sizes)))
         body = []
         for name, tr in traces.items():
             parts = ['   "packs": %s' % json.dumps(tr['packs'], sort_keys=True)]
