@@ -70,7 +70,7 @@ __device__ __forceinline__ void st1(bf16_store_t* p, float v) { *p = (bf16_store
 __device__ __forceinline__ int aide_label2(float z0, float z1) { return (z1 > z0 && expf(z0 - z1) < 1.0f) ? 1 : 0; }
 
 // fp32 soft-max of the C logits of a pixel (planes HW floats apart): z = the logits, p = the probabilities, lse = log sum exp.
-// Shared by the C-class losses, aide_label_map_mc and the ensemble vote, which must agree bit for bit.
+// Shared by the C-class losses, the C-class aide_label_map and the ensemble vote, which must agree bit for bit.
 template <int C>
 __device__ __forceinline__ void soft_terms(const float* __restrict__ zp, int HW, float (&z)[C], float (&p)[C], float& lse) {
     float m = -INFINITY;
@@ -83,6 +83,33 @@ __device__ __forceinline__ void soft_terms(const float* __restrict__ zp, int HW,
 #pragma unroll
     for (int c = 0; c < C; ++c) p[c] *= inv;
     lse = m + logf(s);
+}
+
+// ---- class count of the loss operators (loss.hip, coteach_ext.hip).  Two classes have kernels of their own (one sigmoid of
+// z1 - z0 per pixel), 3 .. AIDE_SEG_MAXC classes the soft-max templates.  Every entry point validates C with load_w and picks
+// its kernel with AIDE_CLASS_SWITCH(C, L2, L): L2 launches the two-class kernel, L(CC) the instantiation for CC classes.
+constexpr int AIDE_SEG_MAXC = 8;      // = aide_seg_max_classes()
+struct ClassW { float w[AIDE_SEG_MAXC]; };
+// The single place that says which class counts the loss kernels serve (min_c = 1: the Dice terms' probability-input form);
+// load_w is the form of the operators with class weights: class_w is a HOST array of C floats, NULL = ones.
+static inline bool seg_classes_ok(int C, int min_c = 2) { return C >= min_c && C <= AIDE_SEG_MAXC; }
+static inline bool load_w(const float* class_w, int C, ClassW& cw, int min_c = 2) {
+    if (!seg_classes_ok(C, min_c)) return false;
+    for (int c = 0; c < AIDE_SEG_MAXC; ++c) cw.w[c] = (class_w && c < C) ? class_w[c] : 1.0f;
+    return true;
+}
+#define AIDE_CLASS_SWITCH(C, L2, L)                                                                \
+    switch (C) {                                                                                   \
+        case 2: { L2; break; }                                                                     \
+        case 3: { L(3); break; } case 4: { L(4); break; } case 5: { L(5); break; }                 \
+        case 6: { L(6); break; } case 7: { L(7); break; } default: { L(8); break; }                \
+    }
+template <int C>
+__device__ __forceinline__ float pick(const float (&v)[C], int k) {   // v[k] without dynamic register indexing
+    float r = v[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) r = (k == c) ? v[c] : r;
+    return r;
 }
 
 static inline int aide_launch_status() { return (int)hipGetLastError(); }

@@ -1,4 +1,4 @@
-// Fused 2-class segmentation losses and co-teaching small-loss selection (gfx950).
+// Fused segmentation losses and co-teaching small-loss selection for 2 .. 8 classes (gfx950).
 //
 // Replaces (reference):
 //   utils/loss2d.py:5-13 CrossEntropyLoss2d, :35-61 DiceLoss, :87-107 MulticlassDiceLoss,
@@ -16,6 +16,22 @@
 // by a one-workgroup finalize kernel; the backward is one elementwise kernel driven by three
 // per-image coefficient vectors (cross-entropy, Dice, consistency-MSE).  Partial sums are combined
 // in a fixed order (no atomics) so the argsort mask is reproducible bit for bit.
+//
+// The shipped scripts of the reference run num_classes = 2 (train_files/trainchaos_comparison_1case.py:121) and the kernels
+// above are specialised for it (one sigmoid per pixel).  The reference's modules themselves are written for any C
+// (`fuseunet(num_classes=...)`, models_twomodalinputs/fuseunet.py:7,41; `nn.CrossEntropyLoss(weight)`, utils/loss2d.py:8;
+// `F.softmax(inputs, dim=1)[:, 1]`, utils/loss2d.py:44-46,65-66,96,106; `MulticlassMSELoss`, utils/loss2d.py:115-117;
+// `sharpen`, train_files/trainchaos_proposed_30cases1labeled.py:97-101; `torch.argmax(softmax)`,
+// trainchaos_comparison_1case.py:262-264).  The `_mc` template kernels are that general form, for C = 3 .. 8:
+//   p = softmax(z) over C planes, lse = log sum exp;  cross-entropy l = w_t (lse - z_t);
+//   Dice and the hard-Dice metrics on p_1 against the target INDEX taken as a number (`tflat = target.float()`,
+//   utils/loss2d.py:50 -- with C > 2 an index 2 counts twice, as in the reference);
+//   consistency term sum_c wm (p_c - q_c)^2; weight map 1 - 4 q_0 q_1 (proposed loop :285-288).
+// They write the SAME eight per-image statistics as seg_stats_kernel, so the finalize kernels (loss values, stable argsort,
+// small-loss selection, backward coefficients) serve both; the backward is again one elementwise pass:
+//   dz_c = g [ cce w_t (p_c - [c = t]) + cdice dDice/dp_1 p_1 ([c = 1] - p_c)
+//              + cmse wm 2 p_c ((p_c - q_c) - sum_j (p_j - q_j) p_j) ].
+// Every entry point takes the class count and picks its kernel itself (AIDE_CLASS_SWITCH, common.h).
 #include "common.h"
 
 namespace {
@@ -64,6 +80,55 @@ __global__ __launch_bounds__(256) void seg_stats_kernel(
             const float p0 = 1.0f - p1;
             const float e1 = p1 - q0[HW + i], e0 = p0 - q0[i];
             acc[S_M] += (double)((wm ? wm[i] : 1.0f) * (e1 * e1 + e0 * e0));
+        }
+        if (p1 >= 0.5f) {
+            acc[S_HP] += 1.0;
+            acc[S_HI] += (double)tf;
+        }
+    }
+    block_sum_d<NS>(acc, sm);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) partials[((long)n * bpi + b) * NS + k] = acc[k];
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void seg_stats_mc_kernel(
+    const float* __restrict__ logits, long l_bs, const long long* __restrict__ targets, long t_bs, const ClassW cw,
+    int ignore_index, const float* __restrict__ pseudo, long p_bs, const float* __restrict__ wmap, long w_bs, int HW,
+    double* __restrict__ partials) {
+    __shared__ double sm[NS * 4];
+    const int n = blockIdx.y, b = blockIdx.x, bpi = gridDim.x;
+    const float* zn = logits + (long)n * l_bs;
+    const long long* t = targets + (long)n * t_bs;
+    const float* qn = pseudo ? pseudo + (long)n * p_bs : nullptr;
+    const float* wm = wmap ? wmap + (long)n * w_bs : nullptr;
+    float w[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) w[c] = cw.w[c];
+    double acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+    for (int i = b * 256 + threadIdx.x; i < HW; i += bpi * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(zn + i, HW, z, p, lse);
+        const long long tv = t[i];
+        const float tf = (float)tv;
+        if (tv != ignore_index && tv >= 0 && tv < C) {
+            const float wt = pick<C>(w, (int)tv);
+            acc[S_CE] += (double)(wt * (lse - pick<C>(z, (int)tv)));
+            acc[S_W] += (double)wt;
+        }
+        const float p1 = p[1];
+        acc[S_I] += (double)(p1 * tf);
+        acc[S_P] += (double)p1;
+        acc[S_T] += (double)tf;
+        if (qn) {
+            float e2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) { const float e = p[c] - qn[(long)c * HW + i]; e2 += e * e; }
+            acc[S_M] += (double)((wm ? wm[i] : 1.0f) * e2);
         }
         if (p1 >= 0.5f) {
             acc[S_HP] += 1.0;
@@ -271,6 +336,54 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(256) void seg_loss_bwd_mc_kernel(
+    const float* __restrict__ logits, long l_bs, const long long* __restrict__ targets, long t_bs, const ClassW cw,
+    int ignore_index, const float* __restrict__ pseudo, long p_bs, const float* __restrict__ wmap, long w_bs, int HW,
+    const double* __restrict__ stats, const float* __restrict__ coef, int N, float smooth,
+    const float* __restrict__ gout, int g_stride, float* __restrict__ dlogits, long d_bs) {
+    const int n = blockIdx.y;
+    const float* zn = logits + (long)n * l_bs;
+    const long long* t = targets + (long)n * t_bs;
+    const float* qn = pseudo ? pseudo + (long)n * p_bs : nullptr;
+    const float* wm = wmap ? wmap + (long)n * w_bs : nullptr;
+    const double* S = stats + n * NS;
+    const float g = gout[n * g_stride];
+    const float cce = g * coef[n], cdice = g * coef[N + n], cmse = g * coef[2 * N + n];
+    const float den = (float)(S[S_P] + S[S_T] + (double)smooth);
+    const float num = (float)(2.0 * S[S_I] + (double)smooth);
+    const float inv_den2 = 1.0f / (den * den);
+    float w[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) w[c] = cw.w[c];
+    float* on = dlogits + (long)n * d_bs;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(zn + i, HW, z, p, lse);
+        const long long tv = t[i];
+        const float tf = (float)tv;
+        const bool on_ce = tv != ignore_index && tv >= 0 && tv < C;
+        const float wce = on_ce ? cce * pick<C>(w, (int)tv) : 0.f;
+        const float gd = cdice * (-(2.0f * tf * den - num) * inv_den2) * p[1];     // x ([c = 1] - p_c)
+        float e[C], ep = 0.f, mw = 0.f;
+        if (qn && cmse != 0.f) {
+            mw = cmse * (wm ? wm[i] : 1.0f) * 2.0f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) { e[c] = p[c] - qn[(long)c * HW + i]; ep += e[c] * p[c]; }
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) e[c] = 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float d = wce * (p[c] - ((int)tv == c ? 1.0f : 0.0f));
+            d += gd * ((c == 1 ? 1.0f : 0.0f) - p[c]);
+            d += mw * p[c] * (e[c] - ep);
+            on[(long)c * HW + i] = d;
+        }
+    }
+}
+
 // reduction='none' cross-entropy map and its backward
 __global__ __launch_bounds__(256) void ce_map_kernel(const float* __restrict__ logits, long l_bs,
                                                      const long long* __restrict__ targets, long t_bs, float w0,
@@ -294,6 +407,35 @@ __global__ __launch_bounds__(256) void ce_map_kernel(const float* __restrict__ l
             const float dd = on ? gout[(long)n * HW + i] * w * (p1 - (float)tv) : 0.f;
             dlogits[(long)n * d_bs + i] = -dd;
             dlogits[(long)n * d_bs + HW + i] = dd;
+        }
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void ce_map_mc_kernel(const float* __restrict__ logits, long l_bs,
+                                                        const long long* __restrict__ targets, long t_bs, const ClassW cw,
+                                                        int ignore_index, int HW, float* __restrict__ out,
+                                                        const float* __restrict__ gout, float* __restrict__ dlogits,
+                                                        long d_bs) {
+    const int n = blockIdx.y;
+    const float* zn = logits + (long)n * l_bs;
+    const long long* t = targets + (long)n * t_bs;
+    float w[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) w[c] = cw.w[c];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(zn + i, HW, z, p, lse);
+        const long long tv = t[i];
+        const bool on = tv != ignore_index && tv >= 0 && tv < C;
+        const float wt = on ? pick<C>(w, (int)tv) : 0.f;
+        if (!gout) {
+            out[(long)n * HW + i] = on ? wt * (lse - pick<C>(z, (int)tv)) : 0.f;
+        } else {
+            const float gw = gout[(long)n * HW + i] * wt;
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                dlogits[(long)n * d_bs + (long)c * HW + i] = gw * (p[c] - ((int)tv == c ? 1.0f : 0.0f));
         }
     }
 }
@@ -323,12 +465,42 @@ __global__ __launch_bounds__(256) void mse_map_kernel(const float* __restrict__ 
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(256) void mse_map_mc_kernel(const float* __restrict__ logits, long l_bs,
+                                                         const float* __restrict__ target, long q_bs, int HW,
+                                                         float* __restrict__ out, const float* __restrict__ gout,
+                                                         float* __restrict__ dlogits, long d_bs) {
+    const int n = blockIdx.y;
+    const float* zn = logits + (long)n * l_bs;
+    const float* q = target + (long)n * q_bs;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(zn + i, HW, z, p, lse);
+        if (!gout) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float e = p[c] - q[(long)c * HW + i];
+                out[(long)n * C * HW + (long)c * HW + i] = e * e;
+            }
+        } else {
+            float ge[C], s = 0.f;                    // d/dz_c = 2 p_c (g_c e_c - sum_j g_j e_j p_j)
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                ge[c] = gout[(long)n * C * HW + (long)c * HW + i] * (p[c] - q[(long)c * HW + i]);
+                s += ge[c] * p[c];
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) dlogits[(long)n * d_bs + (long)c * HW + i] = 2.0f * p[c] * (ge[c] - s);
+        }
+    }
+}
+
 struct PseudoArgs {
     const float* logits[8];
     int K, HW;
     long l_bs;
     float temperature;
-    float* pl;      // [N][2][HW]
+    float* pl;      // [N][C][HW]
     float* wm;      // [N][HW]
 };
 
@@ -355,6 +527,35 @@ __global__ __launch_bounds__(256) void pseudo_label_kernel(const PseudoArgs a) {
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(256) void pseudo_label_mc_kernel(const PseudoArgs a) {
+    const int n = blockIdx.y, HW = a.HW;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        float s[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) s[c] = 0.f;
+        for (int k = 0; k < a.K; ++k) {
+            float z[C], p[C], lse;
+            soft_terms<C>(a.logits[k] + (long)n * a.l_bs + i, HW, z, p, lse);
+#pragma unroll
+            for (int c = 0; c < C; ++c) s[c] += p[c];
+        }
+        float tot = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            s[c] /= (float)a.K;
+            if (a.temperature != 1.0f) s[c] = powf(s[c], a.temperature);
+            tot += s[c];
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            s[c] /= tot;
+            a.pl[(long)n * C * HW + (long)c * HW + i] = s[c];
+        }
+        a.wm[(long)n * HW + i] = 1.0f - 4.0f * s[0] * s[1];
+    }
+}
+
 // label map of the per-case inference loop: argmax(softmax(z), dim=1) for two classes.  The softmax is
 // monotonic, but its rounding merges logits closer than ~2^-25 into equal probabilities, and argmax then
 // returns the FIRST index: label 1 needs z1 > z0 *and* exp(z0 - z1) < 1 in fp32.
@@ -367,6 +568,24 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
     }
 }
 
+// C classes: the first index of the largest PROBABILITY -- logits closer than the softmax rounding merge into equal
+// probabilities and the earlier class wins, as with the two-class kernel
+template <int C>
+__global__ __launch_bounds__(256) void label_map_mc_kernel(const float* __restrict__ logits, long l_bs, int HW,
+                                                           long long* __restrict__ labels, long total) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long n = i / HW, px = i - n * HW;
+        float z[C], p[C], lse;
+        soft_terms<C>(logits + n * l_bs + px, HW, z, p, lse);
+        int best = 0;
+        float pb = p[0];
+#pragma unroll
+        for (int c = 1; c < C; ++c)
+            if (p[c] > pb) { pb = p[c]; best = c; }
+        labels[i] = best;
+    }
+}
+
 int bpi_for(int HW) { return max(1, min((HW + 2047) / 2048, 64)); }
 
 }  // namespace
@@ -376,14 +595,23 @@ extern "C" {
 int aide_seg_loss_blocks(int HW) { return bpi_for(HW); }
 size_t aide_seg_loss_ws_bytes(int N, int HW) { return (size_t)N * bpi_for(HW) * NS * sizeof(double); }
 
+int aide_seg_max_classes(void) { return AIDE_SEG_MAXC; }
+
 // One streaming pass over logits/targets -> per-(image, block) partial statistics in `partials`.
-int aide_seg_stats(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0,
-                   float w1, int ignore_index, const float* pseudo, int64_t p_bs, const float* wmap,
-                   int64_t w_bs, int N, int HW, double* partials, hipStream_t stream) {
-    if (!logits || !targets || !partials || N <= 0 || HW <= 0) return AIDE_ERR_ARG;
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_stats_kernel, dim3(bpi_for(HW), N), dim3(256), 0, stream, logits, (long)l_bs,
-                       targets, (long)t_bs, w0, w1, ignore_index, pseudo, (long)p_bs, wmap, (long)w_bs, HW,
-                       partials);
+// class_w: HOST array of C floats (NULL = all ones)
+int aide_seg_stats(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, const float* class_w,
+                   int C, int ignore_index, const float* pseudo, int64_t p_bs, const float* wmap, int64_t w_bs,
+                   int N, int HW, double* partials, hipStream_t stream) {
+    ClassW cw;
+    if (!logits || !targets || !partials || N <= 0 || HW <= 0 || !load_w(class_w, C, cw)) return AIDE_ERR_ARG;
+    const dim3 grid(bpi_for(HW), N);
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_stats_kernel, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                              (long)t_bs, cw.w[0], cw.w[1], ignore_index, pseudo, (long)p_bs, wmap, (long)w_bs, HW, partials)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_stats_mc_kernel<CC>, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                                 (long)t_bs, cw, ignore_index, pseudo, (long)p_bs, wmap, (long)w_bs, HW, partials)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
@@ -398,13 +626,13 @@ int aide_seg_loss_finalize(const double* partials, int N, int HW, int reduction,
     return aide_launch_status();
 }
 
-// C = classes of the logits the statistics came from (aide_seg_stats: 2, aide_seg_stats_mc: 3 .. 8)
-int aide_coteach_finalize_mc(const double* partials1, const double* partials2, int N, int HW, int C, int variant,
-                             int keep, float w_ce, float w_dice, float smooth, float rate, float w_seg,
-                             float w_cor, double* stats1, double* stats2, float* loss, float* per_image1,
-                             float* per_image2, long long* idx1, long long* idx2, float* coef1, float* coef2,
-                             float* hard_dice, hipStream_t stream) {
-    if (C < 2) return AIDE_ERR_ARG;
+// C = classes of the logits the statistics came from: the consistency map's mean runs over C planes
+int aide_coteach_finalize(const double* partials1, const double* partials2, int N, int HW, int C, int variant,
+                          int keep, float w_ce, float w_dice, float smooth, float rate, float w_seg,
+                          float w_cor, double* stats1, double* stats2, float* loss, float* per_image1,
+                          float* per_image2, long long* idx1, long long* idx2, float* coef1, float* coef2,
+                          float* hard_dice, hipStream_t stream) {
+    if (!seg_classes_ok(C)) return AIDE_ERR_ARG;
     CoteachFinalizeArgs a;
     a.partials1 = partials1; a.partials2 = partials2; a.N = N; a.bpi = bpi_for(HW); a.HW = HW; a.nclass = C;
     a.variant = variant; a.keep = keep; a.w_ce = w_ce; a.w_dice = w_dice; a.smooth = smooth; a.rate = rate;
@@ -415,57 +643,81 @@ int aide_coteach_finalize_mc(const double* partials1, const double* partials2, i
     return aide_launch_status();
 }
 
-int aide_coteach_finalize(const double* partials1, const double* partials2, int N, int HW, int variant,
-                          int keep, float w_ce, float w_dice, float smooth, float rate, float w_seg,
-                          float w_cor, double* stats1, double* stats2, float* loss, float* per_image1,
-                          float* per_image2, long long* idx1, long long* idx2, float* coef1, float* coef2,
-                          float* hard_dice, hipStream_t stream) {
-    return aide_coteach_finalize_mc(partials1, partials2, N, HW, 2, variant, keep, w_ce, w_dice, smooth, rate, w_seg,
-                                    w_cor, stats1, stats2, loss, per_image1, per_image2, idx1, idx2, coef1, coef2,
-                                    hard_dice, stream);
-}
-
-int aide_seg_loss_bwd(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0,
-                      float w1, int ignore_index, const float* pseudo, int64_t p_bs, const float* wmap,
-                      int64_t w_bs, int N, int HW, const double* stats, const float* coef, float smooth,
-                      const float* gout, int g_stride, float* dlogits, int64_t d_bs, hipStream_t stream) {
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_loss_bwd_kernel, dim3(bpi_for(HW) * 4, N), dim3(256), 0, stream, logits,
-                       (long)l_bs, targets, (long)t_bs, w0, w1, ignore_index, pseudo, (long)p_bs, wmap,
-                       (long)w_bs, HW, stats, coef, N, smooth, gout, g_stride, dlogits, (long)d_bs);
+int aide_seg_loss_bwd(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
+                      const float* class_w, int C, int ignore_index, const float* pseudo, int64_t p_bs,
+                      const float* wmap, int64_t w_bs, int N, int HW, const double* stats, const float* coef,
+                      float smooth, const float* gout, int g_stride, float* dlogits, int64_t d_bs,
+                      hipStream_t stream) {
+    ClassW cw;
+    if (!logits || !targets || !stats || !coef || !gout || !dlogits || !load_w(class_w, C, cw)) return AIDE_ERR_ARG;
+    const dim3 grid(bpi_for(HW) * 4, N);
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_loss_bwd_kernel, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                              (long)t_bs, cw.w[0], cw.w[1], ignore_index, pseudo, (long)p_bs, wmap, (long)w_bs, HW, stats, coef, \
+                              N, smooth, gout, g_stride, dlogits, (long)d_bs)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, seg_loss_bwd_mc_kernel<CC>, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                                 (long)t_bs, cw, ignore_index, pseudo, (long)p_bs, wmap, (long)w_bs, HW, stats, coef, N, \
+                                 smooth, gout, g_stride, dlogits, (long)d_bs)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
-// gout == NULL: forward (writes out[N][HW]); else backward (writes dlogits)
-int aide_ce_map(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0, float w1,
-                int ignore_index, int N, int HW, float* out, const float* gout, float* dlogits, int64_t d_bs,
+// gout == NULL: forward (writes out[N][HW]); else backward (writes dlogits[N][C][HW])
+int aide_ce_map(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, const float* class_w,
+                int C, int ignore_index, int N, int HW, float* out, const float* gout, float* dlogits, int64_t d_bs,
                 hipStream_t stream) {
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, ce_map_kernel, dim3(bpi_for(HW) * 4, N), dim3(256), 0, stream, logits, (long)l_bs,
-                       targets, (long)t_bs, w0, w1, ignore_index, HW, out, gout, dlogits, (long)d_bs);
+    ClassW cw;
+    if (!logits || !targets || (!out && !gout) || !load_w(class_w, C, cw)) return AIDE_ERR_ARG;
+    const dim3 grid(bpi_for(HW) * 4, N);
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, ce_map_kernel, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                              (long)t_bs, cw.w[0], cw.w[1], ignore_index, HW, out, gout, dlogits, (long)d_bs)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, ce_map_mc_kernel<CC>, grid, dim3(256), 0, stream, logits, (long)l_bs, targets, \
+                                 (long)t_bs, cw, ignore_index, HW, out, gout, dlogits, (long)d_bs)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
-int aide_mse_map(const float* logits, int64_t l_bs, const float* target, int64_t q_bs, int N, int HW,
+int aide_mse_map(const float* logits, int64_t l_bs, const float* target, int64_t q_bs, int C, int N, int HW,
                  float* out, const float* gout, float* dlogits, int64_t d_bs, hipStream_t stream) {
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, mse_map_kernel, dim3(bpi_for(HW) * 4, N), dim3(256), 0, stream, logits, (long)l_bs,
-                       target, (long)q_bs, HW, out, gout, dlogits, (long)d_bs);
+    if (!logits || !target || (!out && !gout) || !seg_classes_ok(C)) return AIDE_ERR_ARG;
+    const dim3 grid(bpi_for(HW) * 4, N);
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, mse_map_kernel, grid, dim3(256), 0, stream, logits, (long)l_bs, target, \
+                              (long)q_bs, HW, out, gout, dlogits, (long)d_bs)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, mse_map_mc_kernel<CC>, grid, dim3(256), 0, stream, logits, (long)l_bs, target, \
+                                 (long)q_bs, HW, out, gout, dlogits, (long)d_bs)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
-int aide_label_map(const float* logits, int64_t l_bs, int N, int HW, long long* labels, hipStream_t stream) {
-    if (!logits || !labels || N <= 0 || HW <= 0) return AIDE_ERR_ARG;
+int aide_label_map(const float* logits, int64_t l_bs, int C, int N, int HW, long long* labels, hipStream_t stream) {
+    if (!logits || !labels || N <= 0 || HW <= 0 || !seg_classes_ok(C)) return AIDE_ERR_ARG;
     const long total = (long)N * HW;
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, label_map_kernel, dim3((unsigned)min((total + 255) / 256, 8192L)), dim3(256), 0, stream,
-                       logits, (long)l_bs, HW, labels, total);
+    const dim3 grid((unsigned)min((total + 255) / 256, 8192L));
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, label_map_kernel, grid, dim3(256), 0, stream, logits, (long)l_bs, HW, labels, total)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, label_map_mc_kernel<CC>, grid, dim3(256), 0, stream, logits, (long)l_bs, HW, labels, total)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
-int aide_pseudo_label(const float* const* logits, int K, int64_t l_bs, int N, int HW, float temperature,
+int aide_pseudo_label(const float* const* logits, int K, int C, int64_t l_bs, int N, int HW, float temperature,
                       float* pl, float* wm, hipStream_t stream) {
-    if (K < 1 || K > 8) return AIDE_ERR_ARG;
+    if (!logits || K < 1 || K > 8 || !seg_classes_ok(C) || !pl || !wm) return AIDE_ERR_ARG;
     PseudoArgs a;
     for (int k = 0; k < 8; ++k) a.logits[k] = k < K ? logits[k] : nullptr;
     a.K = K; a.HW = HW; a.l_bs = (long)l_bs; a.temperature = temperature; a.pl = pl; a.wm = wm;
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, pseudo_label_kernel, dim3(bpi_for(HW) * 4, N), dim3(256), 0, stream, a);
+    const dim3 grid(bpi_for(HW) * 4, N);
+#define L2 AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, pseudo_label_kernel, grid, dim3(256), 0, stream, a)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, pseudo_label_mc_kernel<CC>, grid, dim3(256), 0, stream, a)
+    AIDE_CLASS_SWITCH(C, L2, L)
+#undef L2
+#undef L
     return aide_launch_status();
 }
 
@@ -589,6 +841,93 @@ __global__ __launch_bounds__(256) void dice_terms_bwd_kernel(const float* __rest
     }
 }
 
+// The same with one-hot targets [N][C][HW] for C = 3 .. 8: one Dice term per class on softmax_c, weighted.
+// partials[n][b][c][3] = { sum p_c t_c, sum p_c, sum t_c }
+template <int C>
+__global__ __launch_bounds__(256) void dice_terms_mc_stats_kernel(const float* __restrict__ x, long x_bs,
+                                                                  const float* __restrict__ t, long t_bs, int HW, int bpi,
+                                                                  double* __restrict__ partials) {
+    __shared__ double sm[3 * C * 4];
+    const int n = blockIdx.y, b = blockIdx.x;
+    const float* xn = x + (long)n * x_bs;
+    const float* tn = t + (long)n * t_bs;
+    double acc[3 * C];
+#pragma unroll
+    for (int k = 0; k < 3 * C; ++k) acc[k] = 0.0;
+    for (int i = b * 256 + threadIdx.x; i < HW; i += bpi * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(xn + i, HW, z, p, lse);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float tv = tn[(long)c * HW + i];
+            acc[3 * c] += (double)(p[c] * tv); acc[3 * c + 1] += (double)p[c]; acc[3 * c + 2] += (double)tv;
+        }
+    }
+    block_sum_d<3 * C>(acc, sm);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 3 * C; ++k) partials[((long)n * bpi + b) * 3 * C + k] = acc[k];
+}
+
+__global__ void dice_terms_mc_finalize_kernel(const double* __restrict__ partials, int N, int bpi, int C, const ClassW cw,
+                                              float smooth, int reduction, double* __restrict__ stats,
+                                              float* __restrict__ per_image, float* __restrict__ out) {
+    for (int e = threadIdx.x; e < N * 3 * C; e += blockDim.x) {
+        const int n = e / (3 * C), k = e - n * 3 * C;
+        double v = 0.0;
+        for (int b = 0; b < bpi; ++b) v += partials[((long)n * bpi + b) * 3 * C + k];
+        stats[e] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // the reference adds the per-class REDUCED terms: mean_c1 + mean_c2 + ... -- for 'none' the per-image vectors
+        double total = 0.0;
+        for (int n = 0; n < N; ++n) {
+            float li = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const double* S = stats + ((long)n * C + c) * 3;
+                const float I = (float)S[0], P = (float)S[1], T = (float)S[2];
+                li += cw.w[c] * (1.0f - (2.0f * I + smooth) / (P + T + smooth));
+            }
+            per_image[n] = li;
+            total += (double)li;
+            if (reduction == 2) out[n] = li;
+        }
+        if (reduction == 0) out[0] = (float)(total / N);
+        else if (reduction == 1) out[0] = (float)total;
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void dice_terms_mc_bwd_kernel(const float* __restrict__ x, long x_bs,
+                                                                const float* __restrict__ t, long t_bs, int HW, int N,
+                                                                const double* __restrict__ stats, const ClassW cw,
+                                                                float smooth, int reduction, const float* __restrict__ g,
+                                                                float* __restrict__ dx, long dx_bs) {
+    const int n = blockIdx.y;
+    const float gi = reduction == 2 ? g[n] : (reduction == 0 ? g[0] / (float)N : g[0]);
+    float c2[C], c1[C];                         // d loss_c / d p_c = -w (2 t D - Nn) / D^2 = c1 - c2 t
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const double* S = stats + ((long)n * C + c) * 3;
+        const float D = (float)S[1] + (float)S[2] + smooth, Nn = 2.0f * (float)S[0] + smooth;
+        const float w = cw.w[c] * gi;
+        c2[c] = w * 2.0f / D;
+        c1[c] = w * Nn / (D * D);
+    }
+    const float* xn = x + (long)n * x_bs;
+    const float* tn = t + (long)n * t_bs;
+    float* dn = dx + (long)n * dx_bs;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        float z[C], p[C], lse;
+        soft_terms<C>(xn + i, HW, z, p, lse);
+        float gc[C], s = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) { gc[c] = c1[c] - c2[c] * tn[(long)c * HW + i]; s += gc[c] * p[c]; }
+#pragma unroll
+        for (int c = 0; c < C; ++c) dn[(long)c * HW + i] = p[c] * (gc[c] - s);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -601,32 +940,52 @@ int aide_onehot_argmax(const float* t, int64_t t_bs, int N, int C, int HW, long 
     return aide_launch_status();
 }
 
-size_t aide_dice_terms_ws_bytes(int N, int HW) { return ((size_t)N * bpi_for(HW) * 6 + (size_t)N * 6) * sizeof(double); }
+size_t aide_dice_terms_ws_bytes(int N, int HW, int C) {
+    return ((size_t)N * bpi_for(HW) * 3 * C + (size_t)N * 3 * C) * sizeof(double);
+}
 
-// K = 1: x = probabilities [N][HW] (batch stride x_bs), t [N][HW];  K = 2: x = logits [N][2][HW], t = one-hot [N][2][HW].
-// ws: aide_dice_terms_ws_bytes; its tail (N * 3 K doubles at ws + N * bpi * 3 K) holds the per-image sums the backward needs.
-int aide_dice_terms_fwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int K, float w0,
-                        float w1, float smooth, int reduction, double* ws, float* per_image, float* out,
+// C = 1: x = probabilities [N][HW] (batch stride x_bs), t [N][HW];  C >= 2: x = logits [N][C][HW], t = one-hot [N][C][HW].
+// ws: aide_dice_terms_ws_bytes; its tail (N * 3 C doubles at ws + N * bpi * 3 C) holds the per-image sums the backward needs.
+int aide_dice_terms_fwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
+                        const float* class_w, float smooth, int reduction, double* ws, float* per_image, float* out,
                         hipStream_t stream) {
-    if (!x || !t || !ws || !per_image || !out || N <= 0 || HW <= 0 || (K != 1 && K != 2) || reduction < 0 || reduction > 2)
+    ClassW cw;
+    if (!x || !t || !ws || !per_image || !out || N <= 0 || HW <= 0 || reduction < 0 || reduction > 2 ||
+        !load_w(class_w, C, cw, 1))
         return AIDE_ERR_ARG;
     const int bpi = bpi_for(HW);
-    double* stats = ws + (size_t)N * bpi * 3 * K;
-    if (K == 1) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_stats_kernel<1>, dim3(bpi, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, bpi, ws);
-    else AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_stats_kernel<2>, dim3(bpi, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, bpi, ws);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, N, bpi, K, w0, w1,
-                       smooth, reduction, stats, per_image, out);
+    double* stats = ws + (size_t)N * bpi * 3 * C;
+#define L12(K) do { \
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_stats_kernel<K>, dim3(bpi, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, bpi, ws); \
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, N, bpi, K, cw.w[0], \
+                           cw.w[1], smooth, reduction, stats, per_image, out); } while (0)
+#define L(CC) do { \
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_mc_stats_kernel<CC>, dim3(bpi, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, bpi, ws); \
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_mc_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, N, bpi, C, cw, \
+                           smooth, reduction, stats, per_image, out); } while (0)
+    if (C == 1) L12(1);
+    else AIDE_CLASS_SWITCH(C, L12(2), L)
+#undef L12
+#undef L
     return aide_launch_status();
 }
 
-int aide_dice_terms_bwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int K, float w0,
-                        float w1, float smooth, int reduction, const double* ws, const float* g, float* dx,
+int aide_dice_terms_bwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
+                        const float* class_w, float smooth, int reduction, const double* ws, const float* g, float* dx,
                         int64_t dx_bs, hipStream_t stream) {
-    if (!x || !t || !ws || !g || !dx || (K != 1 && K != 2)) return AIDE_ERR_ARG;
+    ClassW cw;
+    if (!x || !t || !ws || !g || !dx || !load_w(class_w, C, cw, 1)) return AIDE_ERR_ARG;
     const int bpi = bpi_for(HW);
-    const double* stats = ws + (size_t)N * bpi * 3 * K;
-    if (K == 1) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_bwd_kernel<1>, dim3(bpi * 4, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, N, stats, w0, w1, smooth, reduction, g, dx, (long)dx_bs);
-    else AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_bwd_kernel<2>, dim3(bpi * 4, N), dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, N, stats, w0, w1, smooth, reduction, g, dx, (long)dx_bs);
+    const double* stats = ws + (size_t)N * bpi * 3 * C;
+    const dim3 grid(bpi * 4, N);
+#define L12(K) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_bwd_kernel<K>, grid, dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, N, \
+                                  stats, cw.w[0], cw.w[1], smooth, reduction, g, dx, (long)dx_bs)
+#define L(CC) AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, dice_terms_mc_bwd_kernel<CC>, grid, dim3(256), 0, stream, x, (long)x_bs, t, (long)t_bs, HW, N, \
+                                 stats, cw, smooth, reduction, g, dx, (long)dx_bs)
+    if (C == 1) L12(1);
+    else AIDE_CLASS_SWITCH(C, L12(2), L)
+#undef L12
+#undef L
     return aide_launch_status();
 }
 

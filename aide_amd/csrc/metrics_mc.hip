@@ -3,7 +3,7 @@
 // utils/metrics2d.py:86-196, the same counts for two label volumes of a case, and the running sums of an epoch.
 //
 // Prediction = torch.argmax of the RAW logits (metrics2d.py:89): equal maxima go to the lowest class, a NaN counts as the
-// greatest value and the first NaN wins.  (aide_label_map_mc takes the soft-max first, whose rounding creates other ties.)
+// greatest value and the first NaN wins.  (aide_label_map takes the soft-max first, whose rounding creates other ties.)
 //
 // Counting: every lane holds the class of its pixel in a register; per class a 64-lane ballot of (prediction == c) and one of
 // (target has c) are popcounted -- their AND is the intersection -- into wave-uniform counters.  No per-thread counters and no

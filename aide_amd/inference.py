@@ -29,10 +29,7 @@ def label_map(logits):
         logits = logits.contiguous()
     n, c, h, w = logits.shape
     out = torch.empty(n, h, w, device=logits.device, dtype=torch.int64)
-    if c == 2:
-        check(lib.aide_label_map(ptr(logits), 2 * h * w, n, h * w, ptr(out), stream_ptr()), 'label_map')
-    else:
-        check(lib.aide_label_map_mc(ptr(logits), c * h * w, c, n, h * w, ptr(out), stream_ptr()), 'label_map_mc')
+    check(lib.aide_label_map(ptr(logits), c * h * w, c, n, h * w, ptr(out), stream_ptr()), 'label_map')
     return out
 
 

@@ -1,6 +1,8 @@
 """Shared plumbing for the fused segmentation losses: one statistics pass + one finalize launch in
-the forward, one elementwise launch in the backward (csrc/loss.hip)."""
+the forward, one elementwise launch in the backward (csrc/loss.hip).  Every entry point takes the class count and picks
+its kernel itself; nothing here branches on it."""
 import ctypes
+import functools
 
 import torch
 
@@ -19,7 +21,7 @@ def _logits(x):
     if x.dim() != 4 or not 2 <= x.shape[1] <= MAXC:
         raise NotImplementedError('aide_amd fused losses take logits [N, C, H, W] with 2 <= C <= %d (two classes: the '
                                   'reference configuration, train_files/trainchaos_comparison_1case.py:121, on the '
-                                  'specialised kernels of csrc/loss.hip; 3 .. %d on csrc/loss_mc.hip); got %s'
+                                  'specialised kernels of csrc/loss.hip; 3 .. %d on its soft-max templates); got %s'
                                   % (MAXC, MAXC, tuple(x.shape)))
     if x.dtype != torch.float32:
         raise RuntimeError('aide_amd: logits must be fp32')
@@ -59,46 +61,35 @@ def _targets(t, logits):
 
 
 def class_weights(weight):
-    """The class-weight argument of a loss module as the pair (w0, w1) the two-class entry points take; more than two
-    weights travel as (tuple of C floats, None).  None = unweighted, for any class count."""
+    """The class-weight argument of a loss module as one plain value: None (unweighted, for any class count) or a tuple of
+    2 .. MAXC floats."""
     if weight is None:
-        return 1.0, 1.0
-    w = [float(v) for v in weight]
-    if len(w) == 2:
-        return w[0], w[1]
-    if not 3 <= len(w) <= MAXC:
+        return None
+    w = tuple(float(v) for v in weight)
+    if not 2 <= len(w) <= MAXC:
         raise NotImplementedError('aide_amd fused losses support 2 .. %d classes (got %d class weights)' % (MAXC, len(w)))
-    return tuple(w), None
+    return w
 
 
-def class_w_array(w0, w1, c):
-    """HOST float array of the C class weights for the *_mc entry points (csrc/loss_mc.hip)."""
-    if w1 is None:
-        vals = list(w0)
-    elif (w0, w1) == (1.0, 1.0):
-        vals = [1.0] * c
-    else:
-        vals = [w0, w1]
-    if len(vals) != c:           # nn.CrossEntropyLoss raises for a weight vector that does not match the class count
-        raise RuntimeError('aide_amd: %d class weights for logits with %d classes' % (len(vals), c))
-    return (ctypes.c_float * c)(*vals)
+@functools.lru_cache(maxsize=None)
+def class_w_array(weights, c):
+    """What the loss entry points take as `class_w` for logits with c classes: None (NULL = ones) or a HOST float array of
+    exactly c entries.  Cached per (weights, c): a step builds no array."""
+    if weights is None:
+        return None
+    if len(weights) != c:        # nn.CrossEntropyLoss raises for a weight vector that does not match the class count
+        raise RuntimeError('aide_amd: %d class weights for logits with %d classes' % (len(weights), c))
+    return (ctypes.c_float * c)(*weights)
 
 
-def stats_pass(logits, targets, t_bs, w0, w1, ignore_index, pseudo=None, wmap=None):
+def stats_pass(logits, targets, t_bs, class_w, ignore_index, pseudo=None, wmap=None):
     n, c, h, w = logits.shape
     hw = h * w
     partials = torch.empty(lib.aide_seg_loss_ws_bytes(n, hw) // 8, device=logits.device, dtype=torch.float64)
     p_bs = c * hw if pseudo is not None else 0
     w_bs = hw if wmap is not None else 0
-    if c == 2:
-        if w1 is None:
-            raise RuntimeError('aide_amd: %d class weights for logits with 2 classes' % len(w0))
-        check(lib.aide_seg_stats(ptr(logits), 2 * hw, ptr(targets), t_bs, w0, w1, ignore_index, ptr(pseudo), p_bs,
-                                 ptr(wmap), w_bs, n, hw, ptr(partials), stream_ptr()), 'seg_stats')
-    else:
-        check(lib.aide_seg_stats_mc(ptr(logits), c * hw, ptr(targets), t_bs, class_w_array(w0, w1, c), c, ignore_index,
-                                    ptr(pseudo), p_bs, ptr(wmap), w_bs, n, hw, ptr(partials), stream_ptr()),
-              'seg_stats_mc')
+    check(lib.aide_seg_stats(ptr(logits), c * hw, ptr(targets), t_bs, class_w_array(class_w, c), c, ignore_index,
+                             ptr(pseudo), p_bs, ptr(wmap), w_bs, n, hw, ptr(partials), stream_ptr()), 'seg_stats')
     return partials
 
 
@@ -133,31 +124,22 @@ class SegBackward(torch.autograd.Function):
         g_stride = 0 if g.numel() == 1 else 1
         dl = torch.empty_like(logits)
         pseudo, wmap = pk.get('pseudo'), pk.get('wmap')
-        if c == 2:
-            check(lib.aide_seg_loss_bwd(ptr(logits), 2 * hw, ptr(pk['targets']), pk['t_bs'], pk['w0'], pk['w1'],
-                                        pk['ignore'], ptr(pseudo), 2 * hw if pseudo is not None else 0, ptr(wmap),
-                                        hw if wmap is not None else 0, n, hw, ptr(pk['stats']), ptr(pk['coef']),
-                                        pk['smooth'], ptr(g), g_stride, ptr(dl), 2 * hw, stream_ptr()),
-                  'seg_loss_bwd')
-        else:
-            check(lib.aide_seg_loss_bwd_mc(ptr(logits), c * hw, ptr(pk['targets']), pk['t_bs'],
-                                           class_w_array(pk['w0'], pk['w1'], c), c, pk['ignore'], ptr(pseudo),
-                                           c * hw if pseudo is not None else 0, ptr(wmap),
-                                           hw if wmap is not None else 0, n, hw, ptr(pk['stats']), ptr(pk['coef']),
-                                           pk['smooth'], ptr(g), g_stride, ptr(dl), c * hw, stream_ptr()),
-                  'seg_loss_bwd_mc')
+        check(lib.aide_seg_loss_bwd(ptr(logits), c * hw, ptr(pk['targets']), pk['t_bs'], class_w_array(pk['class_w'], c),
+                                    c, pk['ignore'], ptr(pseudo), c * hw if pseudo is not None else 0, ptr(wmap),
+                                    hw if wmap is not None else 0, n, hw, ptr(pk['stats']), ptr(pk['coef']),
+                                    pk['smooth'], ptr(g), g_stride, ptr(dl), c * hw, stream_ptr()), 'seg_loss_bwd')
         return dl, None, None
 
 
-def seg_loss(logits, targets, w0, w1, ignore_index, reduction, w_ce, w_dice, smooth):
-    """reduction: 0 mean, 1 sum, 2 per-image. Returns (loss, extras dict)."""
+def seg_loss(logits, targets, class_w, ignore_index, reduction, w_ce, w_dice, smooth):
+    """class_w: what class_weights returns.  reduction: 0 mean, 1 sum, 2 per-image.  Returns (loss, extras dict)."""
     logits = _logits(logits)
     targets, t_bs = _targets(targets, logits)
     n, _, h, w = logits.shape
     hw = h * w
     dev = logits.device
     with torch.no_grad():
-        partials = stats_pass(logits, targets, t_bs, w0, w1, ignore_index)
+        partials = stats_pass(logits, targets, t_bs, class_w, ignore_index)
         stats = torch.empty(n * NS, device=dev, dtype=torch.float64)
         per_image = torch.empty(n, device=dev, dtype=torch.float32)
         idx = torch.empty(n, device=dev, dtype=torch.int64)
@@ -170,7 +152,7 @@ def seg_loss(logits, targets, w0, w1, ignore_index, reduction, w_ce, w_dice, smo
                                          ptr(out), ptr(per_image), ptr(idx), ptr(coef), ptr(hard),
                                          stream_ptr()), 'seg_loss_finalize')
         return out if reduction == 2 else out.view(())
-    pack = dict(targets=targets, t_bs=t_bs, w0=w0, w1=w1, ignore=ignore_index, stats=stats, coef=coef,
+    pack = dict(targets=targets, t_bs=t_bs, class_w=class_w, ignore=ignore_index, stats=stats, coef=coef,
                 smooth=smooth)
     loss = SegBackward.apply(logits, finalize, pack)
     return loss, dict(per_image=per_image, argsort=idx, hard_dice=hard.view(()), stats=stats.view(n, NS))
@@ -178,7 +160,7 @@ def seg_loss(logits, targets, w0, w1, ignore_index, reduction, w_ce, w_dice, smo
 
 def coteach_loss(logits1, logits2, targets1, targets2, variant, keep, w_ce, w_dice, smooth=1.0, rate=0.0,
                  w_seg=1.0, w_cor=0.0, pseudo1=None, wmap1=None, pseudo2=None, wmap2=None,
-                 class_w=(1.0, 1.0), ignore_index=255):
+                 class_w=None, ignore_index=255):
     """Two-network cross-selected losses. `targetsK`/`pseudoK`/`wmapK` are what net K is scored against.
     variant: 0 proposed inline step, 1 Coteachingloss_dropimage, 2 Coteachingloss_weightimage."""
     logits1, logits2 = _logits(logits1), _logits(logits2)
@@ -190,14 +172,13 @@ def coteach_loss(logits1, logits2, targets1, targets2, variant, keep, w_ce, w_di
                            % (tuple(logits1.shape), tuple(logits2.shape)))
     hw = h * w
     dev = logits1.device
-    w0, w1 = class_w
     pseudo1 = _dense(pseudo1, (n, c, h, w), 'pseudo label')
     pseudo2 = _dense(pseudo2, (n, c, h, w), 'pseudo label')
     wmap1 = _dense(wmap1, (n, 1, h, w), 'weight map')
     wmap2 = _dense(wmap2, (n, 1, h, w), 'weight map')
     with torch.no_grad():
-        pa1 = stats_pass(logits1, targets1, t1_bs, w0, w1, ignore_index, pseudo1, wmap1)
-        pa2 = stats_pass(logits2, targets2, t2_bs, w0, w1, ignore_index, pseudo2, wmap2)
+        pa1 = stats_pass(logits1, targets1, t1_bs, class_w, ignore_index, pseudo1, wmap1)
+        pa2 = stats_pass(logits2, targets2, t2_bs, class_w, ignore_index, pseudo2, wmap2)
         f64 = dict(device=dev, dtype=torch.float64)
         f32 = dict(device=dev, dtype=torch.float32)
         st1, st2 = torch.empty(n * NS, **f64), torch.empty(n * NS, **f64)
@@ -207,19 +188,13 @@ def coteach_loss(logits1, logits2, targets1, targets2, variant, keep, w_ce, w_di
         i2 = torch.empty(n, device=dev, dtype=torch.int64)
         c1, c2 = torch.empty(3 * n, **f32), torch.empty(3 * n, **f32)
         hard = torch.empty(2, **f32)
-        if c == 2:
-            check(lib.aide_coteach_finalize(ptr(pa1), ptr(pa2), n, hw, variant, keep, w_ce, w_dice, smooth, rate,
-                                            w_seg, w_cor, ptr(st1), ptr(st2), ptr(loss), ptr(pi1), ptr(pi2),
-                                            ptr(i1), ptr(i2), ptr(c1), ptr(c2), ptr(hard), stream_ptr()),
-                  'coteach_finalize')
-        else:
-            check(lib.aide_coteach_finalize_mc(ptr(pa1), ptr(pa2), n, hw, c, variant, keep, w_ce, w_dice, smooth, rate,
-                                               w_seg, w_cor, ptr(st1), ptr(st2), ptr(loss), ptr(pi1), ptr(pi2),
-                                               ptr(i1), ptr(i2), ptr(c1), ptr(c2), ptr(hard), stream_ptr()),
-                  'coteach_finalize_mc')
-    pk1 = dict(targets=targets1, t_bs=t1_bs, w0=w0, w1=w1, ignore=ignore_index, stats=st1, coef=c1,
+        check(lib.aide_coteach_finalize(ptr(pa1), ptr(pa2), n, hw, c, variant, keep, w_ce, w_dice, smooth, rate,
+                                        w_seg, w_cor, ptr(st1), ptr(st2), ptr(loss), ptr(pi1), ptr(pi2),
+                                        ptr(i1), ptr(i2), ptr(c1), ptr(c2), ptr(hard), stream_ptr()),
+              'coteach_finalize')
+    pk1 = dict(targets=targets1, t_bs=t1_bs, class_w=class_w, ignore=ignore_index, stats=st1, coef=c1,
                smooth=smooth, pseudo=pseudo1, wmap=wmap1)
-    pk2 = dict(targets=targets2, t_bs=t2_bs, w0=w0, w1=w1, ignore=ignore_index, stats=st2, coef=c2,
+    pk2 = dict(targets=targets2, t_bs=t2_bs, class_w=class_w, ignore=ignore_index, stats=st2, coef=c2,
                smooth=smooth, pseudo=pseudo2, wmap=wmap2)
     l1 = SegBackward.apply(logits1, loss[0], pk1)
     l2 = SegBackward.apply(logits2, loss[1], pk2)

@@ -52,12 +52,8 @@ class _KLFn(torch.autograd.Function):
     def forward(ctx, z1, z2):
         n, c, h, w = z1.shape
         out = torch.empty(n, h, w, device=z1.device, dtype=torch.float32)
-        if c == 2:
-            check(lib.aide_kl_map(ptr(z1), 2 * h * w, ptr(z2), 2 * h * w, n, h * w, ptr(out), None, None, 0, None, 0,
-                                  stream_ptr()), 'kl_map')
-        else:
-            check(lib.aide_kl_map_mc(ptr(z1), c * h * w, ptr(z2), c * h * w, c, n, h * w, ptr(out), None, None, 0, None, 0,
-                                     stream_ptr()), 'kl_map_mc')
+        check(lib.aide_kl_map(ptr(z1), c * h * w, ptr(z2), c * h * w, c, n, h * w, ptr(out), None, None, 0, None, 0,
+                              stream_ptr()), 'kl_map')
         ctx.save_for_backward(z1, z2)
         return out
 
@@ -67,12 +63,8 @@ class _KLFn(torch.autograd.Function):
         n, c, h, w = z1.shape
         g = g.contiguous().float()
         g1, g2 = torch.empty_like(z1), torch.empty_like(z2)
-        if c == 2:
-            check(lib.aide_kl_map(ptr(z1), 2 * h * w, ptr(z2), 2 * h * w, n, h * w, None, ptr(g), ptr(g1), 2 * h * w,
-                                  ptr(g2), 2 * h * w, stream_ptr()), 'kl_map bwd')
-        else:
-            check(lib.aide_kl_map_mc(ptr(z1), c * h * w, ptr(z2), c * h * w, c, n, h * w, None, ptr(g), ptr(g1), c * h * w,
-                                     ptr(g2), c * h * w, stream_ptr()), 'kl_map_mc bwd')
+        check(lib.aide_kl_map(ptr(z1), c * h * w, ptr(z2), c * h * w, c, n, h * w, None, ptr(g), ptr(g1), c * h * w,
+                              ptr(g2), c * h * w, stream_ptr()), 'kl_map bwd')
         return g1, g2
 
 
@@ -98,7 +90,7 @@ class _RegionCEFn(torch.autograd.Function):
     """mean over images and kept regions of the region CE of `z`, the kept set chosen by the OTHER net's losses."""
 
     @staticmethod
-    def forward(ctx, z, aux, loss_self, loss_other, keep, win=None):
+    def forward(ctx, z, aux, loss_self, loss_other, keep, win):
         n, _, h, w = z.shape
         p = loss_self.numel() // n
         mask, sums, _ = _select(loss_other, loss_self, n, p, k_host=keep)
@@ -113,23 +105,16 @@ class _RegionCEFn(torch.autograd.Function):
         n, c, h, w = z.shape
         coeff = (g.reshape(1).float() / ctx.denom).contiguous()
         dz = torch.empty_like(z)
-        if ctx.win is not None:
-            check(lib.aide_region_ce_bwd_win(ptr(z), c * h * w, ptr(aux), ptr(mask), ptr(coeff), c, n, h, w, ctx.win[0],
-                                             ctx.win[1], ptr(dz), c * h * w, stream_ptr()), 'region_ce_bwd_win')
-        elif c == 2:
-            check(lib.aide_region_ce_bwd(ptr(z), 2 * h * w, ptr(aux), ptr(mask), ptr(coeff), n, h, w, ptr(dz), 2 * h * w,
-                                         stream_ptr()), 'region_ce_bwd')
-        else:
-            check(lib.aide_region_ce_bwd_mc(ptr(z), c * h * w, ptr(aux), ptr(mask), ptr(coeff), c, n, h, w, ptr(dz),
-                                            c * h * w, stream_ptr()), 'region_ce_bwd_mc')
+        check(lib.aide_region_ce_bwd(ptr(z), c * h * w, ptr(aux), ptr(mask), ptr(coeff), c, n, h, w, ctx.win[0],
+                                     ctx.win[1], ptr(dz), c * h * w, stream_ptr()), 'region_ce_bwd')
         return dz, None, None, None, None, None
 
 
 class Coteachingloss_dropregionce(nn.Module):
     """utils/coteach_loss.py:163-196.  Cross entropy on max-pooled regions (logits per class, targets): window = stride =
-    (int(H / int(H * scale)), int(W / int(W * scale))), ceil_mode (:171-174; the default scale 0.5 gives 2x2 windows, which
-    have kernels of their own); per image the `int((1 - forget_rate) * P)` regions with the smallest loss of the other net
-    are kept; mean over all kept."""
+    (int(H / int(H * scale)), int(W / int(W * scale))), ceil_mode (:171-174; the default scale 0.5 gives 2x2 windows, for
+    which the library has kernels of their own); per image the `int((1 - forget_rate) * P)` regions with the smallest loss of
+    the other net are kept; mean over all kept."""
 
     def __init__(self, scale=0.5, reduction='none'):
         super(Coteachingloss_dropregionce, self).__init__()
@@ -149,32 +134,16 @@ class Coteachingloss_dropregionce(nn.Module):
             raise ZeroDivisionError('Coteachingloss_dropregionce: scale %r leaves no patch (the reference divides by zero)' % (self.scale,))
         kh, kw = int(h / ph_), int(w / pw_)
         dev = z1.device
-        if (kh, kw) != (2, 2) or h % 2 or w % 2:
-            # any other window (and odd sizes, whose last window is clipped): the general kernels
-            p = ((h + kh - 1) // kh) * ((w + kw - 1) // kw)
-            keep = int((1 - forget_rate) * p)
-            with torch.no_grad():
-                l1, l2 = torch.empty(n * p, device=dev), torch.empty(n * p, device=dev)
-                a1 = torch.empty(n * p * (c + 1), device=dev, dtype=torch.int32)
-                a2 = torch.empty_like(a1)
-                for z, l, a in ((z1, l1, a1), (z2, l2, a2)):
-                    check(lib.aide_region_ce_fwd_win(ptr(z), c * h * w, ptr(tg), t_bs, c, n, h, w, kh, kw, 255, ptr(l), ptr(a),
-                                                     stream_ptr()), 'region_ce_fwd_win')
-            return (_RegionCEFn.apply(z1, a1, l1, l2, keep, (kh, kw)), _RegionCEFn.apply(z2, a2, l2, l1, keep, (kh, kw)))
-        p = (h // 2) * (w // 2)
+        p = ((h + kh - 1) // kh) * ((w + kw - 1) // kw)                  # ceil_mode: the last row / column of windows is clipped
         keep = int((1 - forget_rate) * p)
         with torch.no_grad():
             l1, l2 = torch.empty(n * p, device=dev), torch.empty(n * p, device=dev)
-            adt = torch.uint8 if c == 2 else torch.int32           # arg-max bookkeeping: a byte for two classes, a word for C
-            a1, a2 = torch.empty(n * p, device=dev, dtype=adt), torch.empty(n * p, device=dev, dtype=adt)
+            a1 = torch.empty(lib.aide_region_ce_aux_bytes(c, n, h, w, kh, kw), device=dev, dtype=torch.uint8)
+            a2 = torch.empty_like(a1)
             for z, l, a in ((z1, l1, a1), (z2, l2, a2)):
-                if c == 2:
-                    check(lib.aide_region_ce_fwd(ptr(z), 2 * h * w, ptr(tg), t_bs, n, h, w, 255, ptr(l), ptr(a),
-                                                 stream_ptr()), 'region_ce_fwd')
-                else:
-                    check(lib.aide_region_ce_fwd_mc(ptr(z), c * h * w, ptr(tg), t_bs, c, n, h, w, 255, ptr(l), ptr(a),
-                                                    stream_ptr()), 'region_ce_fwd_mc')
-        return _RegionCEFn.apply(z1, a1, l1, l2, keep), _RegionCEFn.apply(z2, a2, l2, l1, keep)
+                check(lib.aide_region_ce_fwd(ptr(z), c * h * w, ptr(tg), t_bs, c, n, h, w, kh, kw, 255, ptr(l), ptr(a),
+                                             stream_ptr()), 'region_ce_fwd')
+        return _RegionCEFn.apply(z1, a1, l1, l2, keep, (kh, kw)), _RegionCEFn.apply(z2, a2, l2, l1, keep, (kh, kw))
 
 
 class _DropPixelFn(torch.autograd.Function):
@@ -186,12 +155,8 @@ class _DropPixelFn(torch.autograd.Function):
         n, c, h, w = z1.shape
         hw, nd = h * w, idx.numel()
         v = torch.empty(nd * hw, device=z1.device, dtype=torch.float32)
-        if c == 2:
-            check(lib.aide_droppixel_map(ptr(z1), 2 * hw, ptr(z2), 2 * hw, ptr(tg), t_bs, ptr(idx), nd, hw, which, ptr(v),
-                                         stream_ptr()), 'droppixel_map')
-        else:
-            check(lib.aide_droppixel_map_mc(ptr(z1), c * hw, ptr(z2), c * hw, ptr(tg), t_bs, ptr(idx), nd, c, hw, which, 255,
-                                            ptr(v), stream_ptr()), 'droppixel_map_mc')
+        check(lib.aide_droppixel_map(ptr(z1), c * hw, ptr(z2), c * hw, ptr(tg), t_bs, ptr(idx), nd, c, hw, which, 255,
+                                     ptr(v), stream_ptr()), 'droppixel_map')
         mask, sums, ks = _select(v, v, 1, nd * hw, rr=(-1.0 if k_in is not None else rr), k_in=k_in,
                                  k_host=0, only_positive=True)
         ctx.save_for_backward(z1, z2, tg, idx, mask, ks)
@@ -206,13 +171,9 @@ class _DropPixelFn(torch.autograd.Function):
         hw, nd = h * w, idx.numel()
         coeff = (g.reshape(1).double() / ks[0].double()).float().contiguous()
         g1, g2 = torch.zeros_like(z1), torch.zeros_like(z2)
-        if c == 2:
-            check(lib.aide_droppixel_bwd(ptr(z1), 2 * hw, ptr(z2), 2 * hw, ptr(tg), ctx.t_bs, ptr(idx), nd, hw, ctx.which,
-                                         ptr(mask), ptr(coeff), ptr(g1), ptr(g2), stream_ptr()), 'droppixel_bwd')
-        else:
-            check(lib.aide_droppixel_bwd_mc(ptr(z1), c * hw, ptr(z2), c * hw, ptr(tg), ctx.t_bs, ptr(idx), nd, c, hw,
-                                            ctx.which, 255, ptr(mask), ptr(coeff), ptr(g1), ptr(g2), stream_ptr()),
-                  'droppixel_bwd_mc')
+        check(lib.aide_droppixel_bwd(ptr(z1), c * hw, ptr(z2), c * hw, ptr(tg), ctx.t_bs, ptr(idx), nd, c, hw,
+                                     ctx.which, 255, ptr(mask), ptr(coeff), ptr(g1), ptr(g2), stream_ptr()),
+              'droppixel_bwd')
         return g1, g2, None, None, None, None, None, None
 
 
@@ -248,12 +209,8 @@ def pseudo_label_ensemble(aug_logits, temperature=1.0):
     pl = torch.empty(n, c, h, w, device=lgs[0].device, dtype=torch.float32)
     wm = torch.empty(n, 1, h, w, device=lgs[0].device, dtype=torch.float32)
     arr = (ctypes.c_void_p * len(lgs))(*[t.data_ptr() for t in lgs])
-    if c == 2:
-        check(lib.aide_pseudo_label(arr, len(lgs), 2 * h * w, n, h * w, float(temperature), ptr(pl), ptr(wm),
-                                    stream_ptr()), 'pseudo_label')
-    else:
-        check(lib.aide_pseudo_label_mc(arr, len(lgs), c, c * h * w, n, h * w, float(temperature), ptr(pl), ptr(wm),
-                                       stream_ptr()), 'pseudo_label_mc')
+    check(lib.aide_pseudo_label(arr, len(lgs), c, c * h * w, n, h * w, float(temperature), ptr(pl), ptr(wm),
+                                stream_ptr()), 'pseudo_label')
     return pl, wm
 
 

@@ -1,8 +1,8 @@
 """Drop-in loss modules with the reference's names, constructor and forward signatures
 (utils/loss2d.py:5-154), computed by the fused HIP loss kernels (csrc/loss.hip).
 
-Scope: int64 index targets [N,H,W]; two classes (the reference's hot-path configuration) on the specialised kernels of
-csrc/loss.hip, 3 .. 8 classes on the general form in csrc/loss_mc.hip (same statistics, same finalize kernels).
+Scope: int64 index targets [N,H,W]; 2 .. 8 classes.  The library picks the kernel: two classes (the reference's hot-path
+configuration) run specialised kernels, 3 .. 8 the general soft-max form (same statistics, same finalize kernels).
 `cediceweight` / `ceclassweight` may be CPU tensors exactly as the reference scripts pass them
 (trainchaos_comparison_1case.py:157-166); they are read as host scalars at construction."""
 import torch
@@ -19,32 +19,24 @@ class _CEMap(torch.autograd.Function):
     """reduction='none' cross-entropy map (utils/loss2d.py:8 with reduction='none')."""
 
     @staticmethod
-    def forward(ctx, logits, targets, t_bs, w0, w1, ignore):
+    def forward(ctx, logits, targets, t_bs, class_w, ignore):
         n, c, h, w = logits.shape
         out = torch.empty(n, h, w, device=logits.device, dtype=torch.float32)
-        if c == 2:
-            check(lib.aide_ce_map(ptr(logits), 2 * h * w, ptr(targets), t_bs, w0, w1, ignore, n, h * w, ptr(out),
-                                  None, None, 0, stream_ptr()), 'ce_map')
-        else:
-            check(lib.aide_ce_map_mc(ptr(logits), c * h * w, ptr(targets), t_bs, _seg.class_w_array(w0, w1, c), c, ignore,
-                                     n, h * w, ptr(out), None, None, 0, stream_ptr()), 'ce_map_mc')
+        check(lib.aide_ce_map(ptr(logits), c * h * w, ptr(targets), t_bs, _seg.class_w_array(class_w, c), c, ignore,
+                              n, h * w, ptr(out), None, None, 0, stream_ptr()), 'ce_map')
         ctx.save_for_backward(logits, targets)
-        ctx.cfg = (t_bs, w0, w1, ignore)
+        ctx.cfg = (t_bs, class_w, ignore)
         return out
 
     @staticmethod
     def backward(ctx, g):
         logits, targets = ctx.saved_tensors
-        t_bs, w0, w1, ignore = ctx.cfg
+        t_bs, class_w, ignore = ctx.cfg
         n, c, h, w = logits.shape
         dl = torch.empty_like(logits)
-        if c == 2:
-            check(lib.aide_ce_map(ptr(logits), 2 * h * w, ptr(targets), t_bs, w0, w1, ignore, n, h * w, None,
-                                  ptr(g.contiguous()), ptr(dl), 2 * h * w, stream_ptr()), 'ce_map_bwd')
-        else:
-            check(lib.aide_ce_map_mc(ptr(logits), c * h * w, ptr(targets), t_bs, _seg.class_w_array(w0, w1, c), c, ignore,
-                                     n, h * w, None, ptr(g.contiguous()), ptr(dl), c * h * w, stream_ptr()), 'ce_map_mc_bwd')
-        return dl, None, None, None, None, None
+        check(lib.aide_ce_map(ptr(logits), c * h * w, ptr(targets), t_bs, _seg.class_w_array(class_w, c), c, ignore,
+                              n, h * w, None, ptr(g.contiguous()), ptr(dl), c * h * w, stream_ptr()), 'ce_map_bwd')
+        return dl, None, None, None, None
 
 
 class _MSEMap(torch.autograd.Function):
@@ -54,12 +46,8 @@ class _MSEMap(torch.autograd.Function):
     def forward(ctx, logits, target):
         n, c, h, w = logits.shape
         out = torch.empty_like(logits)
-        if c == 2:
-            check(lib.aide_mse_map(ptr(logits), 2 * h * w, ptr(target), 2 * h * w, n, h * w, ptr(out), None, None,
-                                   0, stream_ptr()), 'mse_map')
-        else:
-            check(lib.aide_mse_map_mc(ptr(logits), c * h * w, ptr(target), c * h * w, c, n, h * w, ptr(out), None, None,
-                                      0, stream_ptr()), 'mse_map_mc')
+        check(lib.aide_mse_map(ptr(logits), c * h * w, ptr(target), c * h * w, c, n, h * w, ptr(out), None, None,
+                               0, stream_ptr()), 'mse_map')
         ctx.save_for_backward(logits, target)
         return out
 
@@ -68,69 +56,38 @@ class _MSEMap(torch.autograd.Function):
         logits, target = ctx.saved_tensors
         n, c, h, w = logits.shape
         dl = torch.empty_like(logits)
-        if c == 2:
-            check(lib.aide_mse_map(ptr(logits), 2 * h * w, ptr(target), 2 * h * w, n, h * w, None,
-                                   ptr(g.contiguous()), ptr(dl), 2 * h * w, stream_ptr()), 'mse_map_bwd')
-        else:
-            check(lib.aide_mse_map_mc(ptr(logits), c * h * w, ptr(target), c * h * w, c, n, h * w, None,
-                                      ptr(g.contiguous()), ptr(dl), c * h * w, stream_ptr()), 'mse_map_mc_bwd')
+        check(lib.aide_mse_map(ptr(logits), c * h * w, ptr(target), c * h * w, c, n, h * w, None,
+                               ptr(g.contiguous()), ptr(dl), c * h * w, stream_ptr()), 'mse_map_bwd')
         return dl, None
 
 
 class _DiceTerms(torch.autograd.Function):
-    """K = 1: DiceLoss on a probability input [N,H,W] (utils/loss2d.py:47-61); K = 2: MulticlassDiceLoss with one-hot
-    targets [N,2,H,W] and class weights on logits [N,2,H,W] (utils/loss2d.py:96-104)."""
+    """c = 1: DiceLoss on a probability input [N,1,HW] (utils/loss2d.py:47-61); c = 2 .. 8: MulticlassDiceLoss with one-hot
+    targets [N,c,H,W] and class weights on logits [N,c,H,W] (utils/loss2d.py:96-104)."""
 
     @staticmethod
-    def forward(ctx, x, t, k, w0, w1, smooth, red):
+    def forward(ctx, x, t, c, class_w, smooth, red):
         n = x.shape[0]
         hw = x.shape[-1] * x.shape[-2]
-        ws = torch.empty(lib.aide_dice_terms_ws_bytes(n, hw) // 8, device=x.device, dtype=torch.float64)
+        ws = torch.empty(lib.aide_dice_terms_ws_bytes(n, hw, c) // 8, device=x.device, dtype=torch.float64)
         per = torch.empty(n, device=x.device, dtype=torch.float32)
         out = torch.empty(n if red == 2 else 1, device=x.device, dtype=torch.float32)
-        check(lib.aide_dice_terms_fwd(ptr(x), k * hw, ptr(t), k * hw, n, hw, k, w0, w1, smooth, red, ptr(ws), ptr(per),
+        cw = _seg.class_w_array(class_w, c)
+        check(lib.aide_dice_terms_fwd(ptr(x), c * hw, ptr(t), c * hw, n, hw, c, cw, smooth, red, ptr(ws), ptr(per),
                                       ptr(out), stream_ptr()), 'dice_terms_fwd')
         ctx.save_for_backward(x, t, ws)
-        ctx.cfg = (k, w0, w1, smooth, red, hw)
+        ctx.cfg = (c, cw, smooth, red, hw)
         return out if red == 2 else out[0]
 
     @staticmethod
     def backward(ctx, g):
         x, t, ws = ctx.saved_tensors
-        k, w0, w1, smooth, red, hw = ctx.cfg
+        c, cw, smooth, red, hw = ctx.cfg
         g = g.contiguous().float().reshape(-1)
         dx = torch.empty_like(x)
-        check(lib.aide_dice_terms_bwd(ptr(x), k * hw, ptr(t), k * hw, x.shape[0], hw, k, w0, w1, smooth, red, ptr(ws),
-                                      ptr(g), ptr(dx), k * hw, stream_ptr()), 'dice_terms_bwd')
-        return dx, None, None, None, None, None, None
-
-
-class _DiceTermsMC(torch.autograd.Function):
-    """MulticlassDiceLoss with one-hot targets [N,C,H,W], C = 3 .. 8 (utils/loss2d.py:96-104): csrc/loss_mc.hip."""
-
-    @staticmethod
-    def forward(ctx, x, t, cw, smooth, red):
-        n, c, h, w = x.shape
-        hw = h * w
-        ws = torch.empty(lib.aide_dice_terms_mc_ws_bytes(n, hw, c) // 8, device=x.device, dtype=torch.float64)
-        per = torch.empty(n, device=x.device, dtype=torch.float32)
-        out = torch.empty(n if red == 2 else 1, device=x.device, dtype=torch.float32)
-        check(lib.aide_dice_terms_mc_fwd(ptr(x), c * hw, ptr(t), c * hw, n, hw, c, cw, smooth, red, ptr(ws), ptr(per),
-                                         ptr(out), stream_ptr()), 'dice_terms_mc_fwd')
-        ctx.save_for_backward(x, t, ws)
-        ctx.cfg = (cw, smooth, red)
-        return out if red == 2 else out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        x, t, ws = ctx.saved_tensors
-        cw, smooth, red = ctx.cfg
-        n, c, h, w = x.shape
-        g = g.contiguous().float().reshape(-1)
-        dx = torch.empty_like(x)
-        check(lib.aide_dice_terms_mc_bwd(ptr(x), c * h * w, ptr(t), c * h * w, n, h * w, c, cw, smooth, red, ptr(ws),
-                                         ptr(g), ptr(dx), c * h * w, stream_ptr()), 'dice_terms_mc_bwd')
-        return dx, None, None, None, None
+        check(lib.aide_dice_terms_bwd(ptr(x), c * hw, ptr(t), c * hw, x.shape[0], hw, c, cw, smooth, red, ptr(ws),
+                                      ptr(g), ptr(dx), c * hw, stream_ptr()), 'dice_terms_bwd')
+        return dx, None, None, None, None, None
 
 
 def _dense_f32(t, shape, what):
@@ -144,15 +101,15 @@ def _dense_f32(t, shape, what):
 class CrossEntropyLoss2d(nn.Module):
     def __init__(self, weight=None, reduction='mean', ignore_index=255):
         super(CrossEntropyLoss2d, self).__init__()
-        self.w0, self.w1 = _seg.class_weights(weight)
+        self.class_w = _seg.class_weights(weight)
         self.reduction, self.ignore_index = reduction, ignore_index
 
     def forward(self, inputs, targets):
         if self.reduction == 'none':
             logits = _seg._logits(inputs)
             t, t_bs = _seg._targets(targets, logits)
-            return _CEMap.apply(logits, t, t_bs, self.w0, self.w1, self.ignore_index)
-        loss, self.last = _seg.seg_loss(inputs, targets, self.w0, self.w1, self.ignore_index,
+            return _CEMap.apply(logits, t, t_bs, self.class_w, self.ignore_index)
+        loss, self.last = _seg.seg_loss(inputs, targets, self.class_w, self.ignore_index,
                                         _RED[self.reduction], 1.0, 0.0, 1.0)
         return loss
 
@@ -175,9 +132,9 @@ class DiceLoss(nn.Module):
                                    % (tuple(input.shape), tuple(target.shape)))
             x = input.contiguous().view(n, 1, -1)
             t = _dense_f32(target.reshape(n, 1, -1), x.shape, 'DiceLoss target')
-            out = _DiceTerms.apply(x, t, 1, 1.0, 1.0, float(self.smooth), red)
+            out = _DiceTerms.apply(x, t, 1, None, float(self.smooth), red)
             return out
-        loss, self.last = _seg.seg_loss(input, target, 1.0, 1.0, 255, red, 0.0, 1.0 if red else 1.0,
+        loss, self.last = _seg.seg_loss(input, target, None, 255, red, 0.0, 1.0 if red else 1.0,
                                         float(self.smooth))
         return loss
 
@@ -191,7 +148,7 @@ class Dice_Loss(nn.Module):
 
     def forward(self, inputs, targets):
         red = 2 if self.reduction == 'none' else _RED[self.reduction]
-        loss, self.last = _seg.seg_loss(inputs, targets, 1.0, 1.0, 255, red, 0.0, 1.0, float(self.smooth))
+        loss, self.last = _seg.seg_loss(inputs, targets, None, 255, red, 0.0, 1.0, float(self.smooth))
         return loss
 
 
@@ -204,15 +161,10 @@ class MulticlassDiceLoss(nn.Module):
         red = 2 if self.reduction == 'none' else _RED[self.reduction]
         if target.dim() > 3:                # utils/loss2d.py:98-104: one Dice term per class, weighted
             logits = _seg._logits(input)
-            w0, w1 = _seg.class_weights(self.weight)
             tgt = _dense_f32(target, logits.shape, 'MulticlassDiceLoss one-hot target')
-            if logits.shape[1] > 2:
-                return _DiceTermsMC.apply(logits, tgt, _seg.class_w_array(w0, w1, logits.shape[1]), float(self.smooth), red)
-            if w1 is None:
-                raise RuntimeError('aide_amd: %d class weights for logits with 2 classes' % len(w0))
-            return _DiceTerms.apply(logits, tgt, 2, w0, w1, float(self.smooth), red)
+            return _DiceTerms.apply(logits, tgt, logits.shape[1], _seg.class_weights(self.weight), float(self.smooth), red)
         # index targets: class-1 Dice only, class weights ignored (utils/loss2d.py:105-106)
-        loss, self.last = _seg.seg_loss(input, target, 1.0, 1.0, 255, red, 0.0, 1.0, float(self.smooth))
+        loss, self.last = _seg.seg_loss(input, target, None, 255, red, 0.0, 1.0, float(self.smooth))
         return loss
 
 
@@ -240,14 +192,14 @@ class CEMDiceLoss(nn.Module):
     def __init__(self, cediceweight=None, ceclassweight=None, diceclassweight=None, reduction='mean'):
         super(CEMDiceLoss, self).__init__()
         self.w_ce, self.w_dice = _pair(cediceweight)
-        self.w0, self.w1 = _seg.class_weights(ceclassweight)
+        self.class_w = _seg.class_weights(ceclassweight)
         if reduction not in _RED:
             raise ValueError("CEMDiceLoss: reduction must be 'mean' or 'sum' (the reference's 'none' mixes a "
                              "[N,H,W] map with a [N] vector)")
         self.reduction = reduction
 
     def forward(self, inputs, targets):
-        loss, self.last = _seg.seg_loss(inputs, targets, self.w0, self.w1, 255, _RED[self.reduction],
+        loss, self.last = _seg.seg_loss(inputs, targets, self.class_w, 255, _RED[self.reduction],
                                         self.w_ce, self.w_dice, 1.0)
         return loss
 
@@ -256,10 +208,10 @@ class CEMDiceLossImage(nn.Module):
     def __init__(self, cediceweight=None, ceclassweight=None, diceclassweight=None, reduction='mean'):
         super(CEMDiceLossImage, self).__init__()
         self.w_ce, self.w_dice = _pair(cediceweight)
-        self.w0, self.w1 = _seg.class_weights(ceclassweight)
+        self.class_w = _seg.class_weights(ceclassweight)
 
     def forward(self, inputs, targets):
-        loss, self.last = _seg.seg_loss(inputs, targets, self.w0, self.w1, 255, 2, self.w_ce, self.w_dice, 1.0)
+        loss, self.last = _seg.seg_loss(inputs, targets, self.class_w, 255, 2, self.w_ce, self.w_dice, 1.0)
         return loss
 
 
@@ -270,13 +222,13 @@ class CEDiceLoss(nn.Module):
     def __init__(self, cediceweight=None, classweight=None, reduction='mean'):
         super(CEDiceLoss, self).__init__()
         self.w_ce, self.w_dice = _pair(cediceweight)
-        self.w0, self.w1 = _seg.class_weights(classweight)
+        self.class_w = _seg.class_weights(classweight)
         if reduction not in _RED:
             raise ValueError("CEDiceLoss: reduction must be 'mean' or 'sum' (the reference's 'none' adds a [N,H,W] map "
                              "to a [N] vector)")
         self.reduction = reduction
 
     def forward(self, inputs, targets):
-        loss, self.last = _seg.seg_loss(inputs, targets, self.w0, self.w1, 255, _RED[self.reduction],
+        loss, self.last = _seg.seg_loss(inputs, targets, self.class_w, 255, _RED[self.reduction],
                                         self.w_ce, self.w_dice, 1.0)
         return loss

@@ -14,7 +14,7 @@ def _counts(inputs, targets, threshold):
     if threshold != 0.5:
         raise NotImplementedError('aide_amd metrics implement the reference default threshold 0.5')
     with torch.no_grad():
-        _, extra = _seg.seg_loss(inputs.detach(), targets, 1.0, 1.0, 255, 2, 1.0, 1.0, 1.0)
+        _, extra = _seg.seg_loss(inputs.detach(), targets, None, 255, 2, 1.0, 1.0, 1.0)
     st = extra['stats']
     hw = float(inputs.shape[2] * inputs.shape[3])
     return extra, st[:, _seg.S_HP], st[:, _seg.S_T], st[:, _seg.S_HI], hw

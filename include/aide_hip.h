@@ -301,17 +301,18 @@ int aide_fill_zero(float* p, int64_t bs, int N, int C, int H, int W, aide_stream
 /* ---- loss-module branches off the hot path ----------------------------------------------------------------------
  * aide_onehot_argmax: targets given one-hot [N][C][HW] -> int64 class indices (utils/loss2d.py:11-12).
  * aide_dice_terms_{fwd,bwd}: per image sum_k w_k (1 - (2 sum p_k t_k + s) / (sum p_k + sum t_k + s)), reduction 0 mean
- * (/N), 1 sum, 2 none.  K = 1: DiceLoss on a PROBABILITY input x [N][HW] (loss2d.py:47-61); K = 2: MulticlassDiceLoss with
- * one-hot targets t [N][2][HW] and class weights (w0, w1) on logits x [N][2][HW] (loss2d.py:96-104; softmax inside).
+ * (/N), 1 sum, 2 none.  C = 1: DiceLoss on a PROBABILITY input x [N][HW] (loss2d.py:47-61); C = 2 .. aide_seg_max_classes():
+ * MulticlassDiceLoss with one-hot targets t [N][C][HW] and class weights on logits x [N][C][HW] (loss2d.py:96-104; softmax
+ * inside).  class_w: HOST array of C floats, NULL = ones.
  * ws: aide_dice_terms_ws_bytes (kept by the caller between fwd and bwd).  g: [1] or [N] upstream gradient. */
 int aide_onehot_argmax(const float* t, int64_t t_bs, int N, int C, int HW, long long* idx, aide_stream_t stream);
-size_t aide_dice_terms_ws_bytes(int N, int HW);
-int aide_dice_terms_fwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int K, float w0,
-                        float w1, float smooth, int reduction, double* ws, float* per_image, float* out,
-                        aide_stream_t stream);
-int aide_dice_terms_bwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int K, float w0,
-                        float w1, float smooth, int reduction, const double* ws, const float* g, float* dx,
-                        int64_t dx_bs, aide_stream_t stream);
+size_t aide_dice_terms_ws_bytes(int N, int HW, int C);
+int aide_dice_terms_fwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
+                        const float* class_w /* HOST */, float smooth, int reduction, double* ws, float* per_image,
+                        float* out, aide_stream_t stream);
+int aide_dice_terms_bwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
+                        const float* class_w /* HOST */, float smooth, int reduction, const double* ws, const float* g,
+                        float* dx, int64_t dx_bs, aide_stream_t stream);
 
 /* ---- stream ordering (host pointers): fork / join between the main stream and the weight-gradient stream as plain C
  * calls, so that a recorded launch sequence (aide_amd/tape.py) can re-issue them.  aide_stream_order(ev, from, to):
@@ -412,121 +413,75 @@ int aide_head1x1_bwd_mixed(const float* dy, int64_t dy_bs, const void* x, int x_
                            void* ws, aide_stream_t stream);
 /* ---- fused segmentation losses / co-teaching selection -----------------------------------------
  * replaces utils/loss2d.py:5-154, utils/coteach_loss.py:94-161, utils/metrics2d.py:8-29 and the
- * inline selection of train_files/trainchaos_proposed_30cases1labeled.py:274-321 */
+ * inline selection of train_files/trainchaos_proposed_30cases1labeled.py:274-321.
+ * The reference's modules are written for any class count (fuseunet(num_classes=...), models_twomodalinputs/
+ * fuseunet.py:7,41; nn.CrossEntropyLoss(weight), utils/loss2d.py:8; softmax(...)[:, 1] in every Dice form,
+ * utils/loss2d.py:44-46,65-66,96,106; MulticlassMSELoss :115-117; sharpen, trainchaos_proposed_30cases1labeled.py:97-101;
+ * argmax(softmax), trainchaos_comparison_1case.py:262-264); its shipped scripts run two.  Every operator has ONE entry
+ * point that takes the class count C = 2 .. aide_seg_max_classes() and picks the kernel itself: two classes run kernels of
+ * their own (one sigmoid of z1 - z0 per pixel), more classes the soft-max templates; any other C is AIDE_ERR_ARG and launches
+ * nothing.  Logits / pseudo labels / gradients are [N][C][HW] planes, class_w is a HOST array of C floats (NULL = ones).
+ * The statistics (partials, stats) have one layout for every C, so aide_seg_loss_finalize needs no C;
+ * aide_coteach_finalize takes it for the mean of the consistency map. */
+int aide_seg_max_classes(void);
 int aide_seg_loss_blocks(int HW);
 size_t aide_seg_loss_ws_bytes(int N, int HW);
-int aide_seg_stats(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0,
-                   float w1, int ignore_index, const float* pseudo, int64_t p_bs, const float* wmap,
-                   int64_t w_bs, int N, int HW, double* partials, aide_stream_t stream);
+int aide_seg_stats(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
+                   const float* class_w /* HOST */, int C, int ignore_index, const float* pseudo, int64_t p_bs,
+                   const float* wmap, int64_t w_bs, int N, int HW, double* partials, aide_stream_t stream);
 int aide_seg_loss_finalize(const double* partials, int N, int HW, int reduction, float w_ce, float w_dice,
                            float smooth, double* stats, float* out, float* per_image, long long* idx,
                            float* coef, float* hard_dice, aide_stream_t stream);
-int aide_coteach_finalize(const double* partials1, const double* partials2, int N, int HW, int variant,
+int aide_coteach_finalize(const double* partials1, const double* partials2, int N, int HW, int C, int variant,
                           int keep, float w_ce, float w_dice, float smooth, float rate, float w_seg,
                           float w_cor, double* stats1, double* stats2, float* loss, float* per_image1,
                           float* per_image2, long long* idx1, long long* idx2, float* coef1, float* coef2,
                           float* hard_dice, aide_stream_t stream);
-int aide_seg_loss_bwd(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0,
-                      float w1, int ignore_index, const float* pseudo, int64_t p_bs, const float* wmap,
-                      int64_t w_bs, int N, int HW, const double* stats, const float* coef, float smooth,
-                      const float* gout, int g_stride, float* dlogits, int64_t d_bs, aide_stream_t stream);
-int aide_ce_map(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs, float w0,
-                float w1, int ignore_index, int N, int HW, float* out, const float* gout, float* dlogits,
-                int64_t d_bs, aide_stream_t stream);
-int aide_mse_map(const float* logits, int64_t l_bs, const float* target, int64_t q_bs, int N, int HW,
+int aide_seg_loss_bwd(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
+                      const float* class_w /* HOST */, int C, int ignore_index, const float* pseudo, int64_t p_bs,
+                      const float* wmap, int64_t w_bs, int N, int HW, const double* stats, const float* coef,
+                      float smooth, const float* gout, int g_stride, float* dlogits, int64_t d_bs,
+                      aide_stream_t stream);
+int aide_ce_map(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
+                const float* class_w /* HOST */, int C, int ignore_index, int N, int HW, float* out,
+                const float* gout, float* dlogits, int64_t d_bs, aide_stream_t stream);
+int aide_mse_map(const float* logits, int64_t l_bs, const float* target, int64_t q_bs, int C, int N, int HW,
                  float* out, const float* gout, float* dlogits, int64_t d_bs, aide_stream_t stream);
-int aide_pseudo_label(const float* const* logits /* HOST array of K device pointers */, int K,
+int aide_pseudo_label(const float* const* logits /* HOST array of K device pointers */, int K, int C,
                       int64_t l_bs, int N, int HW, float temperature, float* pl, float* wm,
                       aide_stream_t stream);
 
-/* ---- the same losses for num_classes = 3 .. aide_seg_max_classes() (csrc/loss_mc.hip) -------------------------------
- * The reference's modules are written for any class count (fuseunet(num_classes=...), models_twomodalinputs/
- * fuseunet.py:7,41; nn.CrossEntropyLoss(weight), utils/loss2d.py:8; softmax(...)[:, 1] in every Dice form,
- * utils/loss2d.py:44-46,65-66,96,106; MulticlassMSELoss :115-117; sharpen, trainchaos_proposed_30cases1labeled.py:97-101;
- * argmax(softmax), trainchaos_comparison_1case.py:262-264); its shipped scripts run two.  Logits / pseudo labels /
- * gradients are [N][C][HW] planes, class_w is a HOST array of C floats (NULL = ones).  The statistics (partials, stats)
- * have the layout of aide_seg_stats, so aide_seg_loss_finalize serves both; aide_coteach_finalize_mc takes C for the
- * mean of the consistency map (aide_coteach_finalize = C 2). */
-int aide_seg_max_classes(void);
-int aide_seg_stats_mc(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
-                      const float* class_w /* HOST */, int C, int ignore_index, const float* pseudo, int64_t p_bs,
-                      const float* wmap, int64_t w_bs, int N, int HW, double* partials, aide_stream_t stream);
-int aide_seg_loss_bwd_mc(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
-                         const float* class_w /* HOST */, int C, int ignore_index, const float* pseudo, int64_t p_bs,
-                         const float* wmap, int64_t w_bs, int N, int HW, const double* stats, const float* coef,
-                         float smooth, const float* gout, int g_stride, float* dlogits, int64_t d_bs,
-                         aide_stream_t stream);
-int aide_coteach_finalize_mc(const double* partials1, const double* partials2, int N, int HW, int C, int variant,
-                             int keep, float w_ce, float w_dice, float smooth, float rate, float w_seg,
-                             float w_cor, double* stats1, double* stats2, float* loss, float* per_image1,
-                             float* per_image2, long long* idx1, long long* idx2, float* coef1, float* coef2,
-                             float* hard_dice, aide_stream_t stream);
-int aide_ce_map_mc(const float* logits, int64_t l_bs, const long long* targets, int64_t t_bs,
-                   const float* class_w /* HOST */, int C, int ignore_index, int N, int HW, float* out,
-                   const float* gout, float* dlogits, int64_t d_bs, aide_stream_t stream);
-int aide_mse_map_mc(const float* logits, int64_t l_bs, const float* target, int64_t q_bs, int C, int N, int HW,
-                    float* out, const float* gout, float* dlogits, int64_t d_bs, aide_stream_t stream);
-int aide_label_map_mc(const float* logits, int64_t l_bs, int C, int N, int HW, long long* labels,
-                      aide_stream_t stream);
-int aide_pseudo_label_mc(const float* const* logits /* HOST array of K device pointers */, int K, int C,
-                         int64_t l_bs, int N, int HW, float temperature, float* pl, float* wm,
-                         aide_stream_t stream);
-/* KLbidirection (utils/coteach_loss.py:85-92), the region cross entropy of Coteachingloss_dropregionce (:163-196; aux is one
- * 32-bit word per 2x2 region here) and the pixel term of Coteachingloss_dropimagedroppixel (:221-252) for C classes; the
- * selections are aide_select_smallest as in the two-class forms.  (Pixelcoreg_Focalloss reads channels 0 and 1 only in the
- * reference itself, utils/reg_loss.py:70-99: it has no C-class form.) */
-int aide_kl_map_mc(const float* z1, int64_t b1, const float* z2, int64_t b2, int C, int N, int HW, float* out,
-                   const float* gout, float* g1, int64_t gb1, float* g2, int64_t gb2, aide_stream_t stream);
-int aide_region_ce_fwd_mc(const float* z, int64_t zb, const long long* t, int64_t tb, int C, int N, int H, int W,
-                          int ignore_index, float* loss, unsigned* aux, aide_stream_t stream);
-int aide_region_ce_bwd_mc(const float* z, int64_t zb, const unsigned* aux, const unsigned char* mask, const float* coeff,
-                          int C, int N, int H, int W, float* dz, int64_t db, aide_stream_t stream);
-int aide_droppixel_map_mc(const float* z1, int64_t b1, const float* z2, int64_t b2, const long long* t, int64_t tb,
-                          const long long* idx, int ndrop, int C, int HW, int which, int ignore_index, float* v,
-                          aide_stream_t stream);
-int aide_droppixel_bwd_mc(const float* z1, int64_t b1, const float* z2, int64_t b2, const long long* t, int64_t tb,
-                          const long long* idx, int ndrop, int C, int HW, int which, int ignore_index,
-                          const unsigned char* mask, const float* coeff, float* g1, float* g2, aide_stream_t stream);
-/* MulticlassDiceLoss with one-hot targets [N][C][HW] (utils/loss2d.py:98-104), one weighted Dice term per class */
-size_t aide_dice_terms_mc_ws_bytes(int N, int HW, int C);
-int aide_dice_terms_mc_fwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
-                           const float* class_w /* HOST */, float smooth, int reduction, double* ws,
-                           float* per_image, float* out, aide_stream_t stream);
-int aide_dice_terms_mc_bwd(const float* x, int64_t x_bs, const float* t, int64_t t_bs, int N, int HW, int C,
-                           const float* class_w /* HOST */, float smooth, int reduction, const double* ws,
-                           const float* g, float* dx, int64_t dx_bs, aide_stream_t stream);
-
-/* ---- remaining co-teaching operators (utils/coteach_loss.py:85-92, 163-196, 198-254), two classes ----
+/* ---- remaining co-teaching operators (utils/coteach_loss.py:85-92, 163-196, 198-254), C = 2 .. aide_seg_max_classes() ----
  * aide_kl_map: KLbidirection, out[n][p] = KL(p1||p2) + KL(p2||p1); with gout (per-pixel upstream gradient) also
  *   the gradients w.r.t. both logit tensors.
- * aide_region_ce_fwd/_bwd: cross entropy on 2x2 max-pooled logits (per class) and targets (:171-179); aux keeps
- *   the arg-max window positions and the pooled target; bwd scatters coeff[0] * mask * dCE to those positions.
+ * aide_region_ce_fwd/_bwd: the region cross entropy of Coteachingloss_dropregionce(scale), which pools logits (per class)
+ *   and targets with MaxPool2d(kernel = stride = (KH, KW), ceil_mode=True), KH = int(H / int(H * scale)) (:171-179) --
+ *   ceil(H / KH) x ceil(W / KW) regions, border windows clipped.  aux (opaque, aide_region_ce_aux_bytes, kept by the caller
+ *   between fwd and bwd) holds the arg-max positions and the pooled target; bwd scatters coeff[0] * mask * dCE to those
+ *   positions.  2x2 windows on even H and W have kernels of their own; the entry picks them.
  * aide_select_smallest: per segment of M values the k smallest candidates (all values, or only those > 0), ties
  *   by lower index (stable argsort, :180-186 / :228-232); k = *k_in | (int64)(rr * candidates) if rr >= 0 | k_host;
  *   mask[M] marks the selection, sums[seg] = fp64 sum of sum_vals over it, ks[seg] = k.
  * aide_droppixel_map/_bwd: v = target * (KL(z1, z2) + CE(z_which, target)) on the images idx[0..ndrop) (:221-227,
- *   :240-246) and its gradient w.r.t. both logit tensors for the selected pixels (g1, g2 pre-zeroed). */
-int aide_kl_map(const float* z1, int64_t b1, const float* z2, int64_t b2, int N, int HW, float* out,
+ *   :240-246) and its gradient w.r.t. both logit tensors for the selected pixels (g1, g2 pre-zeroed).  ignore_index acts
+ *   for C > 2 only: the two-class kernels take every non-zero target as class 1 and do not read it.
+ * (Pixelcoreg_Focalloss reads channels 0 and 1 only in the reference itself, utils/reg_loss.py:70-99: two classes.) */
+int aide_kl_map(const float* z1, int64_t b1, const float* z2, int64_t b2, int C, int N, int HW, float* out,
                 const float* gout, float* g1, int64_t gb1, float* g2, int64_t gb2, aide_stream_t stream);
-int aide_region_ce_fwd(const float* z, int64_t zb, const long long* t, int64_t tb, int N, int H, int W,
-                       int ignore_index, float* loss, unsigned char* aux, aide_stream_t stream);
-int aide_region_ce_bwd(const float* z, int64_t zb, const unsigned char* aux, const unsigned char* mask,
-                       const float* coeff, int N, int H, int W, float* dz, int64_t db, aide_stream_t stream);
-/* the region cross entropy for any pooling window and class count: Coteachingloss_dropregionce(scale) pools with
- * MaxPool2d(kernel = stride = (KH, KW), ceil_mode=True), KH = int(H / int(H * scale)) (utils/coteach_loss.py:171-177) --
- * ceil(H / KH) x ceil(W / KW) regions, border windows clipped; C = 2 .. 8; aux: C + 1 words per region */
-int aide_region_ce_fwd_win(const float* z, int64_t zb, const long long* t, int64_t tb, int C, int N, int H, int W, int KH,
-                           int KW, int ignore_index, float* loss, int* aux, aide_stream_t stream);
-int aide_region_ce_bwd_win(const float* z, int64_t zb, const int* aux, const unsigned char* mask, const float* coeff, int C,
-                           int N, int H, int W, int KH, int KW, float* dz, int64_t db, aide_stream_t stream);
+size_t aide_region_ce_aux_bytes(int C, int N, int H, int W, int KH, int KW);      /* 0: arguments out of range */
+int aide_region_ce_fwd(const float* z, int64_t zb, const long long* t, int64_t tb, int C, int N, int H, int W, int KH,
+                       int KW, int ignore_index, float* loss, void* aux, aide_stream_t stream);
+int aide_region_ce_bwd(const float* z, int64_t zb, const void* aux, const unsigned char* mask, const float* coeff, int C,
+                       int N, int H, int W, int KH, int KW, float* dz, int64_t db, aide_stream_t stream);
 int aide_select_smallest(const float* sel_vals, const float* sum_vals, int64_t seg_stride, int nseg, int M,
                          int64_t k_host, double rr, const long long* k_in, int only_positive, unsigned char* mask,
                          double* sums, long long* ks, aide_stream_t stream);
 int aide_droppixel_map(const float* z1, int64_t b1, const float* z2, int64_t b2, const long long* t, int64_t tb,
-                       const long long* idx, int ndrop, int HW, int which, float* v, aide_stream_t stream);
+                       const long long* idx, int ndrop, int C, int HW, int which, int ignore_index, float* v,
+                       aide_stream_t stream);
 int aide_droppixel_bwd(const float* z1, int64_t b1, const float* z2, int64_t b2, const long long* t, int64_t tb,
-                       const long long* idx, int ndrop, int HW, int which, const unsigned char* mask,
-                       const float* coeff, float* g1, float* g2, aide_stream_t stream);
+                       const long long* idx, int ndrop, int C, int HW, int which, int ignore_index,
+                       const unsigned char* mask, const float* coeff, float* g1, float* g2, aide_stream_t stream);
 
 /* Pixelcoreg_Focalloss / _twomodel (utils/reg_loss.py:58-193): per pixel key = (1-kd)(focal1 + focal2 [+ focal3]) +
  * kd KL(1,2) (focal: gamma 2, lossweight 1), val = focal3 with three nets (z3 != NULL), tf = target as float; the
@@ -538,9 +493,10 @@ int aide_pixelcoreg_bwd(const float* z1, const float* z2, const float* z3, const
                         int HW, float kd, const unsigned char* mask, const float* coeff, float* g1, float* g2,
                         float* g3, aide_stream_t stream);
 
-/* per-case inference (trainchaos_comparison_1case.py:262-264): labels[n][p] = argmax(softmax(logits[n][:,p]))
- * for two classes, int64 like torch.argmax; ties (also those created by the softmax rounding) -> 0 */
-int aide_label_map(const float* logits, int64_t l_bs, int N, int HW, long long* labels, aide_stream_t stream);
+/* per-case inference (trainchaos_comparison_1case.py:262-264): labels[n][p] = argmax(softmax(logits[n][:,p])) for
+ * C = 2 .. aide_seg_max_classes(), int64 like torch.argmax; ties (also those created by the softmax rounding) -> the
+ * lowest class */
+int aide_label_map(const float* logits, int64_t l_bs, int C, int N, int HW, long long* labels, aide_stream_t stream);
 
 /* ---- per-case evaluation: largest 3-D connected component, confusion sums ----------------------
  * replaces the CPU post-processing of the per-case loop: keep_largest_connected_components (skimage
@@ -740,7 +696,7 @@ int aide_image_bank_targets(const unsigned char* plane, int64_t K, int64_t H, in
  * prediction, t = one-hot of the target.  C = 2 .. 8; integer sums, the same bits from run to run. */
 /* counts[N][C][3] (int64) from logits [N][C][HW] fp32 (image stride l_bs floats, channels HW apart; N <= 65535, C * HW < 2^31).
  * Prediction = torch.argmax(logits, dim=1) of the RAW logits (:89): equal maxima -> the lowest class; NaN is the greatest
- * value and the first NaN wins.  (aide_label_map_mc is argmax(softmax(.)): its rounding merges close logits, so it has other
+ * value and the first NaN wins.  (aide_label_map is argmax(softmax(.)): its rounding merges close logits, so it has other
  * ties.)  target (image stride t_bs elements), by t_kind: 0 one-hot [N][C][HW] float, 1 one-hot int64, 2 one-hot uint8 -- the
  * loaders' 0/1-valued masks: any non-zero value is read as 1, soft targets are outside the contract; 3 class index [N][HW]
  * int64 -- an index outside [0, C) belongs to no class, its pixel still counts in sum i.  counts need no zero-fill by the
@@ -776,9 +732,9 @@ int aide_mc_metrics_accumulate(const long long* counts, int64_t N, int C, int64_
 int aide_view_stack(const float* x, int64_t x_bs, float* y, int64_t y_bs, const int* views /* HOST [V] */, int V,
                     int N, int C, int H, int W, aide_stream_t stream);
 /* The soft vote of K members (C = 2 .. aide_seg_max_classes()): for output pixel (n, i, j) and member k = 0 .. K - 1 in order,
- * the C logits at the position views[k] maps (i, j) to, their fp32 soft-max as aide_label_map_mc takes it, added to a
+ * the C logits at the position views[k] maps (i, j) to, their fp32 soft-max as aide_label_map takes it for C > 2, added to a
  * per-class fp32 sum; probs (NULL, or [N][C][H][W] with image stride p_bs) = sum * (1 / K); labels[N][H][W] = the FIRST index
- * of the largest sum.  One member under view 0 gives the labels of aide_label_map / aide_label_map_mc. */
+ * of the largest sum.  One member under view 0 gives the labels of aide_label_map. */
 int aide_ensemble_vote(const float* const* logits /* HOST array of K device pointers, each [N][C][H][W] in its member's view frame */,
                        const int* views /* HOST [K] */, int K, int64_t l_bs, int N, int C, int H, int W,
                        long long* labels /* [N][H][W] */, float* probs /* NULL or [N][C][H][W] */, int64_t p_bs,

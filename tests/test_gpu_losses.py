@@ -403,3 +403,22 @@ def test_loss_branches_off_the_hot_path(dev):
                 v2.backward()
             close(v2, fx[key], what=key + ' (flattened)')
             close(x2.grad.reshape(x.shape), fx[key + '/grad'], what=key + ' grad (flattened)')
+
+
+def test_unweighted_is_unit_weights_two_classes(dev):
+    """Two classes: ceclassweight=None (the library's NULL = ones) and [1.0, 1.0] (a two-entry host array) are the same
+    launch, so loss and gradient agree bit for bit.  HW = 2300: two blocks per image, the last one partial, no multiple of 4."""
+    from aide_amd import utils as U
+    g = torch.Generator().manual_seed(46)
+    z = (torch.randn(3, 2, 46, 50, generator=g) * 3).to(dev)
+    t = (torch.rand(3, 46, 50, generator=g) > 0.6).long()
+    t[0, 0, :5] = 255
+    t = t.to(dev)
+    got = []
+    for cw in (None, [1.0, 1.0]):
+        zz = z.clone().requires_grad_(True)
+        v = U.CEMDiceLoss(cediceweight=[0.7, 1.6], ceclassweight=cw)(zz, t)
+        v.backward()
+        got.append((v.detach(), zz.grad))
+    assert torch.isfinite(got[0][0]) and float(got[0][1].abs().max()) > 0
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])

@@ -1,5 +1,5 @@
-"""-m gpu: num_classes = 3 .. 8 through the drop-in modules (csrc/loss_mc.hip, the head kernels for K <= 8), against the
-values and gradients of the real reference (tests/golden/g17_multiclass.npz, oracle/gen_golden.py::g17_multiclass).
+"""-m gpu: num_classes = 3 .. 8 through the drop-in modules (the soft-max templates of csrc/loss.hip and
+csrc/coteach_ext.hip, the head kernels for K <= 8), against the values and gradients of the real reference (tests/golden/g17_multiclass.npz, oracle/gen_golden.py::g17_multiclass).
 fp32 tolerance 1e-4 relative (north star: 1e-3); labels and selection indices exact."""
 import os
 
@@ -197,3 +197,15 @@ def test_class_count_limits(dev):
         U.CrossEntropyLoss2d(weight=torch.tensor([1.0, 2.0, 3.0]))(z[:, :4].contiguous(), t)
     with pytest.raises(NotImplementedError):     # Pixelcoreg_Focalloss reads channels 0 and 1 only in the reference itself
         U.Pixelcoreg_Focalloss_twomodel()(z[:, :3].contiguous(), z[:, :3].contiguous(), t, 0.2, 0.5, dev)
+    # the library's own guard: a class count outside 2 .. aide_seg_max_classes() is a negative code and launches nothing
+    from aide_amd._lib import lib
+    from aide_amd.ops import ptr, stream_ptr
+    assert lib.aide_seg_max_classes() == 8
+    for c in (1, 9):
+        zc = z[:, :c].contiguous()
+        part = torch.full((lib.aide_seg_loss_ws_bytes(2, 64) // 8,), -7.0, dtype=torch.float64, device=dev)
+        out = torch.full((2, 8, 8), -7.0, device=dev)
+        assert lib.aide_seg_stats(ptr(zc), c * 64, ptr(t), 64, None, c, 255, None, 0, None, 0, 2, 64, ptr(part), stream_ptr()) < 0
+        assert lib.aide_kl_map(ptr(zc), c * 64, ptr(zc), c * 64, c, 2, 64, ptr(out), None, None, 0, None, 0, stream_ptr()) < 0
+        torch.cuda.synchronize()
+        assert bool((part == -7.0).all()) and bool((out == -7.0).all())
