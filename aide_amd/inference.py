@@ -419,24 +419,29 @@ def keep_largest_batched(labels, slice_start, num_classes=None, stats=False):
 
 def case_dice_rule(sums, labelled=None, n_select=0):
     """The host statement of `aide_label_refresh_select` (numpy): int64 sums [K,4] -> (dice float32 [K], rank int32 [K],
-    selected uint8 [K]).  dice = float32(float64(2 * sum p*t) / float64(sum p + sum t)); rank ascending with NaN greatest and
-    equal values by the lower index; selected = rank < n_select and not labelled."""
+    selected uint8 [K]).  dice = float32(float64(2 * sum p*t) / float64(sum p + sum t)); rank and selected by `_rank_select`
+    with every case that is not labelled eligible."""
     sums = np.asarray(sums, np.int64).reshape(-1, 4)
     with np.errstate(divide='ignore', invalid='ignore'):
         dice = (np.float64(2) * sums[:, 1].astype(np.float64) / (sums[:, 2] + sums[:, 3]).astype(np.float64)).astype(np.float32)
-    rank, sel = _rank_select(dice, labelled, n_select)
+    rank, sel = _rank_select(dice, _unlabelled(labelled, len(dice)), n_select)
     return dice, rank, sel
 
 
-def _rank_select(dice, labelled, n_select):
-    """float32 scores [K] -> (rank int32 [K]: ascending, NaN greatest, equal values by the lower index; selected uint8 [K])"""
+def _unlabelled(labelled, k):
+    return np.ones(k, bool) if labelled is None else ~np.asarray(labelled).astype(bool)
+
+
+def _rank_select(dice, eligible, n_select):
+    """THE ranking of every pseudo-label refresh, on the host: float32 scores [K] -> (rank int32 [K]: ascending, NaN greatest,
+    equal values -- two NaNs included -- by the lower index; flag uint8 [K] = rank < n_select and eligible).  The tie rule is this
+    project's, not parity: the reference's `Tensor.sort()` is not stable."""
     key = np.where(np.isnan(dice), np.float32(np.inf), dice)
     nan = np.isnan(dice).astype(np.int64)
-    order = np.lexsort((np.arange(len(dice)), key, nan))          # last key first: NaN flag, value, case index
+    order = np.lexsort((np.arange(len(dice)), key, nan))          # last key first: NaN flag, value, index
     rank = np.empty(len(dice), np.int32)
     rank[order] = np.arange(len(dice), dtype=np.int32)
-    lab = np.zeros(len(dice), bool) if labelled is None else np.asarray(labelled).astype(bool)
-    return rank, ((rank < int(n_select)) & ~lab).astype(np.uint8)
+    return rank, ((rank < int(n_select)) & eligible).astype(np.uint8)
 
 
 def _palette(palette, c, what):
@@ -500,92 +505,74 @@ def case_dice_rule_classes(counts, labelled=None, n_select=0):
         present += has
     with np.errstate(divide='ignore', invalid='ignore'):
         dice = (total / present.astype(np.float64)).astype(np.float32)        # no organ: 0 / 0, the NaN of the binary rule
-    rank, sel = _rank_select(dice, labelled, n_select)
+    rank, sel = _rank_select(dice, _unlabelled(labelled, k), n_select)
     return d.astype(np.float32), dice, rank, sel
 
 
-def _device_args(filt, slice_start, bank_plane, labelled):
-    if not (isinstance(bank_plane, torch.Tensor) and bank_plane.is_cuda and bank_plane.dtype == torch.uint8
-            and bank_plane.is_contiguous() and tuple(bank_plane.shape) == tuple(filt.shape)):
-        raise RuntimeError('evaluate_label_maps: bank_plane must be a contiguous uint8 HIP tensor shaped like the labels')
-    if labelled is not None and not (isinstance(labelled, torch.Tensor) and labelled.is_cuda
-                                     and labelled.dtype == torch.uint8 and labelled.numel() == slice_start.numel() - 1):
-        raise RuntimeError('evaluate_label_maps: labelled must be a uint8 HIP tensor [K]')
-
-
-def _evaluate_label_maps_classes(labels, slice_start, bank_plane, c, palette, labelled, n_select, keep_largest):
-    c = int(c)
-    if not 2 <= c <= 8:
-        raise ValueError('evaluate_label_maps: num_classes %d, 2 .. 8 are supported' % c)
-    if isinstance(labels, torch.Tensor) and labels.is_cuda:
-        if isinstance(palette, torch.Tensor):     # the bank's device table; the owner has checked its values
-            if not (palette.is_cuda and palette.dtype == torch.int32 and palette.dim() == 1 and palette.numel() == c
-                    and palette.is_contiguous()):
-                raise ValueError('evaluate_label_maps: a device palette must be a contiguous int32 HIP tensor [%d]' % c)
-            pal = palette
-        else:
-            pal = torch.tensor(_palette(palette, c, 'evaluate_label_maps'), dtype=torch.int32).pin_memory().to(
-                labels.device, non_blocking=True)
-        filt = keep_largest_batched(labels, slice_start, num_classes=c) if keep_largest else labels.to(torch.uint8).contiguous()
-        _device_args(filt, slice_start, bank_plane, labelled)
-        k = slice_start.numel() - 1
-        dev = filt.device
-        counts = torch.empty(k, c, 3, device=dev, dtype=torch.int64)
-        cd = torch.empty(k, c, device=dev, dtype=torch.float32)
-        dice = torch.empty(k, device=dev, dtype=torch.float32)
-        rank = torch.empty(k, device=dev, dtype=torch.int32)
-        sel = torch.empty(k, device=dev, dtype=torch.uint8)
-        check(lib.aide_case_class_counts_batched(ptr(filt), ptr(bank_plane), ptr(slice_start), k, *filt.shape, ptr(pal), c,
-                                                 ptr(counts), stream_ptr()), 'case_class_counts_batched')
-        check(lib.aide_label_refresh_select_classes(ptr(counts), ptr(labelled) if labelled is not None else None, k, c,
-                                                    int(n_select), ptr(cd), ptr(dice), ptr(rank), ptr(sel), stream_ptr()),
-              'label_refresh_select_classes')
-        return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
+def _device_palette(palette, c, device):
+    """the int32 HIP table of a C-class palette: the owner's own (it has checked the values), or one made from the bytes"""
     if isinstance(palette, torch.Tensor):
-        palette = palette.tolist()
-    pal = _palette(palette, c, 'evaluate_label_maps')
-    lab = np.asarray(labels)
-    st = _starts(slice_start, lab.shape[0])
-    filt = keep_largest_batched(lab, st, num_classes=c) if keep_largest else lab.astype(np.uint8)
-    counts = case_class_counts(filt, bank_plane, st, pal)
-    cd, dice, rank, sel = case_dice_rule_classes(counts, labelled, n_select)
-    return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
+        if not (palette.is_cuda and palette.dtype == torch.int32 and palette.dim() == 1 and palette.numel() == c
+                and palette.is_contiguous()):
+            raise ValueError('evaluate_label_maps: a device palette must be a contiguous int32 HIP tensor [%d]' % c)
+        return palette
+    return torch.tensor(_palette(palette, c, 'evaluate_label_maps'), dtype=torch.int32).pin_memory().to(device, non_blocking=True)
 
 
 def evaluate_label_maps(labels, slice_start, bank_plane, match=63, labelled=None, n_select=0, keep_largest=True,
                         num_classes=None, palette=None):
     """Label maps [S_total,H,W] of K concatenated cases against one plane of the pseudo-label bank (uint8 [S_total,H,W]):
     dict(filtered uint8 [S_total,H,W], sums int64 [K,4] = N / sum p*t / sum p / sum t with t = (bank byte == match),
-    dice float32 [K], rank int32 [K], selected uint8 [K]).  On HIP tensors seven launches, all results stay on the device and
+    dice float32 [K], rank int32 [K], selected uint8 [K]).  On HIP tensors eight launches, all results stay on the device and
     nothing synchronises; slice_start / labelled are then device tables (int64 [K+1] / uint8 [K]).  On numpy / CPU inputs the
     same integers through the CPU filter.
     num_classes=C (2 .. 8) with palette = C distinct bytes (ValueError otherwise; `match` is not used): the multi-organ form.
-    The filter is `keep_largest_batched(num_classes=C)` (keep_largest=False: a plain uint8 cast), the result
+    The filter is `keep_largest_batched(num_classes=C)` (keep_largest=False: a plain uint8 cast either way), the result
     dict(filtered, counts int64 [K,C,3], class_dice float32 [K,C], dice, rank, selected) of `case_class_counts` and
     `case_dice_rule_classes`; on HIP tensors `aide_case_class_counts_batched` and `aide_label_refresh_select_classes`, with
     the same no-synchronisation rule (the palette may then be the int32 HIP table its owner keeps)."""
-    if num_classes is not None:
-        return _evaluate_label_maps_classes(labels, slice_start, bank_plane, num_classes, palette, labelled, n_select,
-                                            keep_largest)
-    if palette is not None:
+    c = None if num_classes is None else int(num_classes)
+    if c is None and palette is not None:
         raise ValueError('evaluate_label_maps: palette goes with num_classes')
+    if c is not None and not 2 <= c <= 8:
+        raise ValueError('evaluate_label_maps: num_classes %d, 2 .. 8 are supported' % c)
     if isinstance(labels, torch.Tensor) and labels.is_cuda:
-        filt = keep_largest_batched(labels, slice_start) if keep_largest else labels.to(torch.uint8).contiguous()
-        _device_args(filt, slice_start, bank_plane, labelled)
+        pal = _device_palette(palette, c, labels.device) if c else None
+        filt = keep_largest_batched(labels, slice_start, num_classes=c) if keep_largest else labels.to(torch.uint8).contiguous()
+        if not (isinstance(bank_plane, torch.Tensor) and bank_plane.is_cuda and bank_plane.dtype == torch.uint8
+                and bank_plane.is_contiguous() and tuple(bank_plane.shape) == tuple(filt.shape)):
+            raise RuntimeError('evaluate_label_maps: bank_plane must be a contiguous uint8 HIP tensor shaped like the labels')
         k = slice_start.numel() - 1
+        if labelled is not None and not (isinstance(labelled, torch.Tensor) and labelled.is_cuda
+                                         and labelled.dtype == torch.uint8 and labelled.numel() == k):
+            raise RuntimeError('evaluate_label_maps: labelled must be a uint8 HIP tensor [K]')
         dev = filt.device
-        sums = torch.empty(k, 4, device=dev, dtype=torch.int64)
         dice = torch.empty(k, device=dev, dtype=torch.float32)
         rank = torch.empty(k, device=dev, dtype=torch.int32)
         sel = torch.empty(k, device=dev, dtype=torch.uint8)
-        check(lib.aide_case_confusion_batched(ptr(filt), ptr(bank_plane), ptr(slice_start), k, *filt.shape, int(match),
-                                              ptr(sums), stream_ptr()), 'case_confusion_batched')
-        check(lib.aide_label_refresh_select(ptr(sums), ptr(labelled) if labelled is not None else None, k, int(n_select),
-                                            ptr(dice), ptr(rank), ptr(sel), stream_ptr()), 'label_refresh_select')
+        out = (ptr(dice), ptr(rank), ptr(sel), stream_ptr())
+        planes = (ptr(filt), ptr(bank_plane), ptr(slice_start), k) + tuple(filt.shape)
+        lab = ptr(labelled) if labelled is not None else None
+        if c:
+            counts = torch.empty(k, c, 3, device=dev, dtype=torch.int64)
+            cd = torch.empty(k, c, device=dev, dtype=torch.float32)
+            check(lib.aide_case_class_counts_batched(*planes, ptr(pal), c, ptr(counts), stream_ptr()), 'case_class_counts_batched')
+            check(lib.aide_label_refresh_select_classes(ptr(counts), lab, k, c, int(n_select), ptr(cd), *out),
+                  'label_refresh_select_classes')
+            return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
+        sums = torch.empty(k, 4, device=dev, dtype=torch.int64)
+        check(lib.aide_case_confusion_batched(*planes, int(match), ptr(sums), stream_ptr()), 'case_confusion_batched')
+        check(lib.aide_label_refresh_select(ptr(sums), lab, k, int(n_select), *out), 'label_refresh_select')
         return dict(filtered=filt, sums=sums, dice=dice, rank=rank, selected=sel)
+    if c:
+        pal = _palette(palette.tolist() if isinstance(palette, torch.Tensor) else palette, c, 'evaluate_label_maps')
     lab = np.asarray(labels)
     st = _starts(slice_start, lab.shape[0])
-    filt = keep_largest_batched(lab, st) if keep_largest else lab.astype(np.uint8)
+    filt = keep_largest_batched(lab, st, num_classes=c) if keep_largest else lab.astype(np.uint8)
+    if c:
+        counts = case_class_counts(filt, bank_plane, st, pal)
+        cd, dice, rank, sel = case_dice_rule_classes(counts, labelled, n_select)
+        return dict(filtered=filt, counts=counts, class_dice=cd, dice=dice, rank=rank, selected=sel)
     t = np.asarray(bank_plane) == match
     sums = np.zeros((len(st) - 1, 4), np.int64)
     for k, (a, b) in enumerate(zip(st, st[1:])):
@@ -613,18 +600,15 @@ MAX_IMAGES = 1 << 20
 def image_dice_rule(sums, labelled=None, n_select=0):
     """The host statement of `aide_image_refresh_select` (numpy): int64 sums [K,4] -> (dice float32 [K], rank int32 [K],
     written uint8 [K]).  dice = 0.0 where sum p + sum t == 0 (Dice2d, :137-138: never NaN), else float32(float64(2 * sum p*t)
-    / float64(sum p + sum t)); rank ascending with equal values by the lower image index; written = rank < n_select and
-    sum p > 0 (:418 `if save_data.sum() > 0`) and not labelled."""
+    / float64(sum p + sum t)); rank and written by `_rank_select`, an image being eligible when sum p > 0 (:418 `if
+    save_data.sum() > 0`) and it is not labelled."""
     sums = np.asarray(sums, np.int64).reshape(-1, 4)
     uni = sums[:, 2] + sums[:, 3]
     dice = np.zeros(len(sums), np.float32)
     nz = uni != 0
     dice[nz] = ((2 * sums[nz, 1]).astype(np.float64) / uni[nz].astype(np.float64)).astype(np.float32)
-    order = np.lexsort((np.arange(len(dice)), dice))
-    rank = np.empty(len(dice), np.int32)
-    rank[order] = np.arange(len(dice), dtype=np.int32)
-    lab = np.zeros(len(dice), bool) if labelled is None else np.asarray(labelled).astype(bool)
-    return dice, rank, ((rank < int(n_select)) & (sums[:, 2] > 0) & ~lab).astype(np.uint8)
+    rank, written = _rank_select(dice, (sums[:, 2] > 0) & _unlabelled(labelled, len(dice)), n_select)
+    return dice, rank, written
 
 
 def _image_eval_args(what, src, score_rows, gate, k0, pred, sums):

@@ -23,7 +23,7 @@ in the prediction or the pseudo-label, and the selected cases get `palette[predi
 (`aide_label_bank_targets_index`).
 
 `ImageLabelBank` is the per-IMAGE form of the kidney and breast scripts (no component filter, Dice2d with union == 0 -> 0.0,
-`--update_percent`, an empty prediction is never written; `aide_image_*` of csrc/labelbank_image.hip): see its docstring."""
+`--update_percent`, an empty prediction is never written; `aide_image_*` of csrc/labelbank.hip): see its docstring."""
 import os
 
 import numpy as np
@@ -108,48 +108,46 @@ class PseudoLabelBank(object):
         device: no host synchronisation (`selected` never leaves it).  With num_classes the label maps carry class values
         0 .. C - 1, the filter is the per-class one, and a selected case gets `palette[filtered]` (a value >= C, which only an
         unfiltered map can hold, writes palette[0])."""
-        from ._lib import lib, check
-        from .ops import ptr, stream_ptr
         write = refresh_gate(epoch, warmup_epoch)
         c = self.num_classes
+        dev = self.device is not None
+        start, labelled, palette = (self._start, self._labelled, self._palette) if dev else \
+            (self.slice_start, self.labelled_host, self.palette)
         for n, labels in enumerate((labels1, labels2)):
-            if self.device is not None:
-                if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
-                    raise RuntimeError('PseudoLabelBank: the bank is on %s, the label maps must be too' % self.device)
-                r = evaluate_label_maps(labels, self._start, self.bank[n], self.match, self._labelled, self.n_select, keep_largest,
-                                        num_classes=c, palette=self._palette if c else None)
-                self._dice[n].copy_(r['dice'])
-                self.rank[n].copy_(r['rank'])
-                self.selected[n].copy_(r['selected'])
-                if c:
-                    self._class_dice[n].copy_(r['class_dice'])
-                if write:
-                    f = r['filtered']
-                    if c:
-                        check(lib.aide_label_bank_update_classes(ptr(f), ptr(r['selected']), ptr(self._start), self.K, *f.shape,
-                                                                 ptr(self._palette), c, ptr(self.bank[n]), stream_ptr()),
-                              'label_bank_update_classes')
-                    else:
-                        check(lib.aide_label_bank_update(ptr(f), ptr(r['selected']), ptr(self._start), self.K, *f.shape, LIVER,
-                                                         ptr(self.bank[n]), stream_ptr()), 'label_bank_update')
-                    self.modified[n].bitwise_or_(r['selected'])
-            else:
-                r = evaluate_label_maps(np.asarray(labels), self.slice_start, self.bank[n], self.match, self.labelled_host,
-                                        self.n_select, keep_largest, num_classes=c, palette=self.palette if c else None)
-                self._dice[n], self.rank[n], self.selected[n] = r['dice'], r['rank'], r['selected']
-                if c:
-                    self._class_dice[n] = r['class_dice']
-                    lut = np.full(256, self.palette[0], np.uint8)
-                    lut[:c] = self.palette
-                if write:
-                    for k in np.flatnonzero(r['selected']):
-                        a, b = self.slice_start[k], self.slice_start[k + 1]
-                        if c:
-                            self.bank[n][a:b] = lut[r['filtered'][a:b]]
-                        else:
-                            self.bank[n][a:b] = (r['filtered'][a:b] * LIVER).astype(np.uint8)     # :549-550
-                    self.modified[n] |= r['selected']
+            if dev and not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+                raise RuntimeError('PseudoLabelBank: the bank is on %s, the label maps must be too' % self.device)
+            r = evaluate_label_maps(labels if dev else np.asarray(labels), start, self.bank[n], self.match, labelled, self.n_select,
+                                    keep_largest, num_classes=c, palette=palette if c else None)
+            self._dice[n][...], self.rank[n][...], self.selected[n][...] = r['dice'], r['rank'], r['selected']
+            if c:
+                self._class_dice[n][...] = r['class_dice']
+            if write:
+                self._rewrite(self.bank[n], r['filtered'], r['selected'])
+                modified = self.modified[n]
+                modified |= r['selected']
         return write
+
+    def _rewrite(self, plane, filtered, selected):
+        """the selected cases' slices of `plane` = the byte map of `filtered`: `* LIVER` (:549-550), with num_classes
+        `palette[v]` and palette[0] for a value >= C.  On the device `selected` is read there."""
+        c = self.num_classes
+        if self.device is not None:
+            from ._lib import lib, check
+            from .ops import ptr, stream_ptr
+            args = (ptr(filtered), ptr(selected), ptr(self._start), self.K) + tuple(filtered.shape)
+            if c:
+                check(lib.aide_label_bank_update_classes(*args, ptr(self._palette), c, ptr(plane), stream_ptr()),
+                      'label_bank_update_classes')
+            else:
+                check(lib.aide_label_bank_update(*args, LIVER, ptr(plane), stream_ptr()), 'label_bank_update')
+            return
+        lut = (np.arange(256) * LIVER).astype(np.uint8)
+        if c:
+            lut[:] = self.palette[0]
+            lut[:c] = self.palette
+        for k in np.flatnonzero(selected):
+            a, b = self.slice_start[k], self.slice_start[k + 1]
+            plane[a:b] = lut[filtered[a:b]]
 
     def refresh(self, net1, net2, inputs, epoch, warmup_epoch, batch_size=16, views=None):
         """inputs = (inphase[, outphase]), each [S_total,3,H,W]: both networks (eval mode) predict every slice, then

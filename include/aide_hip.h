@@ -620,11 +620,11 @@ int aide_case_confusion_batched(const unsigned char* p, const unsigned char* tar
  * fp64 and rounded once (a numpy float64 stored into a float32 tensor, :488; 0 / 0 -> NaN).  rank[k] = position of case k in
  * ascending order of dice, NaN greatest (torch's sort), equal values by the lower case index (this library's rule: the
  * reference's sort is not stable).  selected[k] = rank[k] < n_select && !labelled[k] (labelled may be NULL).  K <= 4096.
- * One launch of one workgroup. */
+ * Two launches: the score, then the ranking that all three *_refresh_select* entry points share. */
 int aide_label_refresh_select(const long long* sums, const unsigned char* labelled, int64_t K, int64_t n_select, float* dice,
                               int* rank, unsigned char* selected, aide_stream_t stream);
 /* bank_plane[slices of k] = pred * scale (uint8; :548-551 with scale 63) for every case with selected[k] != 0, read on the
- * device.  One launch. */
+ * device.  One launch, a 1-D grid over (case, chunk): the rewrite kernel of all three *_bank_update* entry points. */
 int aide_label_bank_update(const unsigned char* pred, const unsigned char* selected, const long long* slice_start, int64_t K,
                            int64_t S_total, int64_t H, int64_t W, int scale, unsigned char* bank_plane, aide_stream_t stream);
 /* out[N][npal][H][W] (int64) = one_hot_mask of bank_plane[slice_idx[n]] over the palette (npal = 1 .. 8 device ints): the
@@ -644,7 +644,7 @@ int aide_case_class_counts_batched(const unsigned char* pred, const unsigned cha
  * (0 / 0 -> NaN).  dice[k] = float32 of the fp64 mean of those fp64 quotients over the foreground classes c = 1 .. C - 1 with
  * P + T > 0, summed in ascending c and divided by their number; NaN when there is none.  An organ absent from prediction and
  * pseudo-label alike is left out, one present in only one of them scores 0.  With C = 2 the bits of aide_label_refresh_select.
- * rank, selected, labelled, the K <= 4096 limit and the single workgroup are that function's. */
+ * rank, selected, labelled, the K <= 4096 limit and the two launches are that function's. */
 int aide_label_refresh_select_classes(const long long* counts, const unsigned char* labelled, int64_t K, int C, int64_t n_select,
                                       float* class_dice, float* dice, int* rank, unsigned char* selected, aide_stream_t stream);
 /* bank_plane[slices of k] = palette[pred] for every case with selected[k] != 0, read on the device; a predicted value >= C
@@ -678,7 +678,7 @@ int aide_image_eval_labels(const void* labels, int is_u8, const unsigned char* s
  * fp64 (Dice2d stored into a float32 tensor, :392).  rank[k] = position of image k in ascending order of dice, equal values
  * by the lower image index (this library's rule: the reference's sort is not stable; NaN, which Dice2d cannot give, would
  * rank greatest).  written[k] = rank[k] < n_select && sums[k][2] > 0 && !labelled[k] (labelled may be NULL): the `if
- * save_data.sum() > 0` of :418.  Two launches for any K. */
+ * save_data.sum() > 0` of :418.  Two launches for any K, the ranking being aide_label_refresh_select's. */
 int aide_image_refresh_select(const long long* sums, const unsigned char* labelled, int64_t K, int64_t n_select, float* dice,
                               int* rank, unsigned char* written, aide_stream_t stream);
 /* plane[k] = pred[k] * scale (uint8; 255 for the breast PNGs, 1 for the kidney volumes) for every image with written[k] != 0,

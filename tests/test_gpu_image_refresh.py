@@ -1,4 +1,4 @@
-"""-m gpu: the per-image pseudo-label refresh on the device (aide_amd/csrc/labelbank_image.hip, aide_amd/labelbank.py
+"""-m gpu: the per-image pseudo-label refresh on the device (aide_amd/csrc/labelbank.hip,aide_amd/labelbank.py
 ImageLabelBank).  The device bank reproduces fixture g24 (the reference's own statements, tools/gen_golden_image_refresh.py) and
 the numpy bank byte for byte, the fused epilogue's labels are `label_map`'s, ranking and write flags follow the documented rule
 for K up to 70001, `refresh` equals per-image prediction + the host rule, and the kidney / breast loops run with the switch set

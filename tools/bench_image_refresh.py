@@ -5,8 +5,7 @@
 Per K (planes of size x size):
   epilogue  `aide_image_eval_logits` over all K images in batches of 16 (as `ImageLabelBank.refresh` issues it, the forward
             excluded): bytes moved = K * HW * (8 logits + 1 score + 1 label), against the 8 TB/s of the data sheet
-  select    `aide_image_refresh_select`; at K = 4096 -- the only size both accept -- beside the single-workgroup
-            `aide_label_refresh_select` of the per-case bank (a ratio, no threshold)
+  select    `aide_image_refresh_select`
   update    `aide_image_bank_update` with a quarter of the images written: bytes = 2 * written * HW
   refresh   `ImageLabelBank.refresh_from_labels` + `image_dice()` (label maps on the device, forward excluded) against the same
             rule the reference's way: per image a `.cpu().numpy()` of the label map and of the target, Dice2d, on 16 host
@@ -47,8 +46,6 @@ def main():
     ap.add_argument('--reps', type=int, default=9)
     ap.add_argument('--host-images', type=int, nargs='*', default=[4096])
     a = ap.parse_args()
-    from aide_amd._lib import lib, check
-    from aide_amd.ops import ptr, stream_ptr
     from aide_amd.inference import image_eval_logits, image_refresh_select, image_bank_update
     from aide_amd.labelbank import ImageLabelBank
     dev = torch.device('cuda:0')
@@ -73,12 +70,7 @@ def main():
         sums = bank._sums[0]
         out = (torch.empty(K, device=dev), torch.empty(K, device=dev, dtype=torch.int32), torch.empty(K, device=dev, dtype=torch.uint8))
         med, lo, hi = dev_ms(lambda: image_refresh_select(sums, None, bank.n_select, out=out), a.reps)
-        line = 'K %6d  select    %9.3f ms (%.3f .. %.3f)' % (K, med, lo, hi)
-        if K <= 4096:
-            old = dev_ms(lambda: check(lib.aide_label_refresh_select(ptr(sums), None, K, bank.n_select, ptr(out[0]), ptr(out[1]),
-                                                                     ptr(out[2]), stream_ptr()), 'select'), a.reps)
-            line += '   single-workgroup aide_label_refresh_select %9.3f ms: x %.2f' % (old[0], old[0] / med)
-        print(line)
+        print('K %6d  select    %9.3f ms (%.3f .. %.3f)' % (K, med, lo, hi))
         written = (torch.arange(K, device=dev) % 4 == 0).to(torch.uint8)
         plane = orig.clone()
         med, lo, hi = dev_ms(lambda: image_bank_update(bank._pred[0], written, 255, plane), a.reps)
