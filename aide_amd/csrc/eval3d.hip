@@ -35,6 +35,14 @@
 // class value 1 .. C - 1 (the value read at the root), out[i] = the voxel's own class where its root is that class's winner.
 // The 3 C control words per case (keys, root counts, area sums) are cleared by one memset in front of launch 1: five
 // launches and one memset whatever C and K are.
+//
+// Case post-processing on the single volume reuses the pipeline (the invariant above holds for all of it: integers,
+// atomicMin / atomicOr / atomicMax / atomicAdd only, nothing depends on the schedule, no workgroup waits for another):
+//   k largest, size floor  (aide_keep_components3d) launches 1 - 3, one select pass per rank, and a write that compares
+//                          key(find(i)) with the slot's threshold
+//   holes                  (aide_fill_holes3d) launches 1 - 3 with the connectivity predicate "value == 0" (launches 1 - 2 take
+//                          the predicate as a template parameter), one word per root that records what the blob touches, a
+//                          write that fills where the word is exactly one class
 #include "common.h"
 
 namespace {
@@ -193,11 +201,27 @@ __device__ __forceinline__ int find_plain(const int* parent, int x) {
     return x;
 }
 
+// The connectivity predicate of launches 1 - 2: `at` maps the stored value to the value the union-find sees (0: the voxel is in
+// no set; face neighbours of EQUAL non-zero mapped value join), `joins(axis)` says whether faces across a logical axis connect.
+// Equal: the label itself, every axis -- the component filters.  Background<T>: 1 on the voxels whose stored value (T = int64
+// or uint8) is exactly 0, so the sets are the blobs of background; axis `cut` (-1: none) does not connect: 2-D slices along it.
+struct Equal {
+    __device__ __forceinline__ long long at(const View& g, long off) const { return g.v[off]; }
+    __device__ __forceinline__ bool joins(int) const { return true; }
+};
+template <typename T>
+struct Background {
+    int cut;
+    __device__ __forceinline__ T raw(const View& g, long off) const { return reinterpret_cast<const T*>(g.v)[off]; }
+    __device__ __forceinline__ long long at(const View& g, long off) const { return raw(g, off) == 0; }
+    __device__ __forceinline__ bool joins(int axis) const { return axis != cut; }
+};
+
 // ---- 1 local: the tile at logical origin (o0, o1, o2); out-of-volume voxels read as background ----
 // A thread's column: TZ voxels along the slab axis from the tile's voxel (c0, c1, c2), each step LZ local indices,
 // slab_stride elements and slab_nodes nodes further on; `depth` of them lie inside the volume
-template <int SLAB>
-__device__ __forceinline__ void tile_local(const View& g, int o0, int o1, int o2, int* __restrict__ parent,
+template <int SLAB, class P>
+__device__ __forceinline__ void tile_local(const View& g, const P& pred, int o0, int o1, int o2, int* __restrict__ parent,
                                            int* __restrict__ area, long long* val, int* lp, int* cnt) {
     constexpr int L0 = LS0<SLAB>, L1 = LS1<SLAB>, LZ = SLAB == 0 ? L0 : 1;
     const int t = threadIdx.x, p = t >> 4, q = t & 15;
@@ -212,7 +236,7 @@ __device__ __forceinline__ void tile_local(const View& g, int o0, int o1, int o2
     for (int z = 0; z < TZ; ++z) {
         const int e = e0 + z * LZ;
         long long v = 0;
-        if (z < depth) v = g.v[off0 + z * slab_stride];
+        if (z < depth) v = pred.at(g, off0 + z * slab_stride);
         val[e] = v;
         lp[e] = v != 0 ? e : -1;
         cnt[e] = 0;
@@ -225,9 +249,9 @@ __device__ __forceinline__ void tile_local(const View& g, int o0, int o1, int o2
         const int e = e0 + z * LZ;
         const long long v = val[e];
         if (v == 0) continue;
-        if (l2 > 0 && val[e - 1] == v) lds_unite(lp, e - 1, e);
-        if (l1 > 0 && val[e - L1] == v) lds_unite(lp, e - L1, e);
-        if (l0 > 0 && val[e - L0] == v) lds_unite(lp, e - L0, e);
+        if (l2 > 0 && pred.joins(2) && val[e - 1] == v) lds_unite(lp, e - 1, e);
+        if (l1 > 0 && pred.joins(1) && val[e - L1] == v) lds_unite(lp, e - L1, e);
+        if (l0 > 0 && pred.joins(0) && val[e - L0] == v) lds_unite(lp, e - L0, e);
     }
     __syncthreads();
     int root[TZ];
@@ -251,8 +275,8 @@ __device__ __forceinline__ void tile_local(const View& g, int o0, int o1, int o2
     }
 }
 
-template <class G>
-__global__ __launch_bounds__(256) void lcc_local_kernel(G geo, int* __restrict__ parent, int* __restrict__ area,
+template <class G, class P>
+__global__ __launch_bounds__(256) void lcc_local_kernel(G geo, P pred, int* __restrict__ parent, int* __restrict__ area,
                                                         unsigned long long* __restrict__ ctrl) {
     __shared__ long long val[TILE];
     __shared__ int lp[TILE];
@@ -262,14 +286,14 @@ __global__ __launch_bounds__(256) void lcc_local_kernel(G geo, int* __restrict__
     for (int tile = geo.tile_begin(); tile < geo.tile_end(g); tile += geo.tile_step()) {
         int o0, o1, o2;
         geo.tile_origin(tile, o0, o1, o2);
-        tile_local<G::SLAB>(g, o0, o1, o2, parent, area, val, lp, cnt);
+        tile_local<G::SLAB>(g, pred, o0, o1, o2, parent, area, val, lp, cnt);
     }
 }
 
 // ---- 2 border: the three lower faces of a tile, in thread coordinates: q face (TZ x 16 pairs), p face (TZ x 16),
 // z face (16 x 16) ----
-template <int SLAB>
-__device__ __forceinline__ void tile_border(const View& g, int o0, int o1, int o2, int* __restrict__ parent) {
+template <int SLAB, class P>
+__device__ __forceinline__ void tile_border(const View& g, const P& pred, int o0, int o1, int o2, int* __restrict__ parent) {
     for (int k = threadIdx.x; k < 2 * TZ * TQ + TQ * TQ; k += 256) {
         int z, p, q, dz = 0, dp = 0, dq = 0;
         if (k < TZ * TQ) {
@@ -286,22 +310,23 @@ __device__ __forceinline__ void tile_border(const View& g, int o0, int o1, int o
         to_logical<SLAB>(dz, dp, dq, e0, e1, e2);
         const int a0 = o0 + l0, a1 = o1 + l1, a2 = o2 + l2;
         if (a0 < e0 || a1 < e1 || a2 < e2) continue;          // the face lies on the volume's edge
+        if (!pred.joins(e0 ? 0 : e1 ? 1 : 2)) continue;
         if (!g.has(a0, a1, a2)) continue;
         const long off = g.off(a0, a1, a2);
-        const long long v = g.v[off];
+        const long long v = pred.at(g, off);
         if (v == 0) continue;
-        if (g.v[off - g.off(e0, e1, e2)] != v) continue;
+        if (pred.at(g, off - g.off(e0, e1, e2)) != v) continue;
         unite(parent, g.node(a0 - e0, a1 - e1, a2 - e2), g.node(a0, a1, a2));
     }
 }
 
-template <class G>
-__global__ __launch_bounds__(256) void lcc_border_kernel(G geo, int* __restrict__ parent) {
+template <class G, class P>
+__global__ __launch_bounds__(256) void lcc_border_kernel(G geo, P pred, int* __restrict__ parent) {
     const View g = geo.view();
     for (int tile = geo.tile_begin(); tile < geo.tile_end(g); tile += geo.tile_step()) {
         int o0, o1, o2;
         geo.tile_origin(tile, o0, o1, o2);
-        tile_border<G::SLAB>(g, o0, o1, o2, parent);
+        tile_border<G::SLAB>(g, pred, o0, o1, o2, parent);
     }
 }
 
@@ -367,10 +392,15 @@ struct Acc {                                      // a thread's running key, roo
     unsigned cnt[SLOTS<M>], vox[SLOTS<M>];        // a sum of areas of distinct roots never exceeds the voxel count < 2^31
 };
 
-// root i of area ar goes to `slot`: larger area first, then the lower root
+// the key of root i of area ar: larger area first, then the lower root
+__device__ __forceinline__ unsigned long long root_key(int i, int ar) {
+    return ((unsigned long long)(unsigned)ar << 32) | (unsigned)(0x7fffffff - i);
+}
+
+// root i of area ar goes to `slot`
 template <Mode M>
 __device__ __forceinline__ void acc_add(Acc<M>& a, int slot, int i, int ar) {
-    const unsigned long long key = ((unsigned long long)(unsigned)ar << 32) | (unsigned)(0x7fffffff - i);
+    const unsigned long long key = root_key(i, ar);
 #pragma unroll
     for (int j = 0; j < SLOTS<M>; ++j)
         if (slot == j) {
@@ -486,6 +516,183 @@ __global__ __launch_bounds__(256) void lcc_write_kernel(G geo, const int* __rest
         }
         out[at] = (unsigned char)o;
     });
+}
+
+// ---- the k largest components with a size floor (aide_keep_components3d; the single volume) ----
+// Launches 1 - 3, then one select pass per rank, then write.  Keys are unique per root, so "the first k of the order" is
+// "key >= the k-th largest key of the slot": pass 0 is lcc_select_kernel itself (max key, and the flag or the stats sums), pass
+// j >= 1 takes per slot the max key strictly below pass j - 1's (0 when the slot has no further root, and 0 from then on).
+// Control words: 0 .. 3 MAXC - 1 are pass 0's as ctrl_words lays them out; the keys of pass j >= 1, slot s, are word
+// 3 MAXC + (j - 1) MAXC + s.  One memset clears them all.
+constexpr int MAXK = 8;
+constexpr int KC_WORDS = 3 * MAXC + (MAXK - 1) * MAXC;
+
+// per class value 1 .. C - 1 (BINARY: entry 1): top_k (0: every blob) and min_voxels << 32, a key no smaller blob reaches
+struct Rule {
+    int k[MAXC];
+    unsigned long long floor[MAXC];
+};
+
+template <Mode M>
+__device__ __forceinline__ long kc_keys(int pass, int C) {
+    return pass == 0 ? ctrl_words<M>(C).key : 3 * MAXC + (long)(pass - 1) * MAXC;
+}
+
+template <class G, Mode M>                        // M: BINARY or CLASSES
+__global__ __launch_bounds__(256) void kc_next_kernel(G geo, const int* __restrict__ parent, const int* __restrict__ area, int C,
+                                                      int pass, unsigned long long* __restrict__ ctrl) {
+    __shared__ unsigned long long bound[SLOTS<M>];
+    const int live = M == BINARY ? 1 : C - 1;
+    if ((int)threadIdx.x < live) bound[threadIdx.x] = ctrl[kc_keys<M>(pass - 1, C) + threadIdx.x];
+    __syncthreads();
+    const View g = geo.view();
+    Acc<M> a = {};
+    geo.select_nodes(g, [&](int i, auto value_off, long) {
+        if (parent[i] != i) return;
+        int slot = 0;
+        if (M != BINARY) {
+            const int c = class_of(g.v[value_off()], C);
+            if (!c) return;
+            slot = c - 1;
+        }
+        const unsigned long long key = root_key(i, area[i]);
+#pragma unroll
+        for (int j = 0; j < SLOTS<M>; ++j)
+            if (slot == j && key < bound[j]) a.key[j] = umax64(a.key[j], key);
+    });
+    acc_commit(a, live, ctrl, Ctrl{kc_keys<M>(pass, C), 0, 0});   // (BINARY: the flag's count stays 0, no atomic for it)
+}
+
+// out[i] = 1 (the voxel's class) where key(find(i)) reaches its slot's threshold = max(k-th largest key, floor).  CLASSES
+// with stats: rows (blobs, voxels) from pass 0's words by block 0, and every kept root adds its area to the row's third word
+// (cleared before the launches): summed over the wave first, one atomic per (wave, class)
+template <Mode M>                                 // M: BINARY or CLASSES
+__global__ __launch_bounds__(256) void kc_write_kernel(Strided geo, const int* __restrict__ parent, const int* __restrict__ area,
+                                                       int C, Rule rule, const unsigned long long* __restrict__ ctrl,
+                                                       unsigned char* __restrict__ out, long long* __restrict__ stats) {
+    __shared__ unsigned long long thr[MAXC];      // by class value; ~0: nothing of the class is kept
+    const int c = threadIdx.x;
+    if (c < MAXC) {
+        unsigned long long t = ~0ull;
+        if (c >= 1 && c < (M == BINARY ? 2 : C)) {
+            const int k = rule.k[c];
+            t = umax64(k ? ctrl[kc_keys<M>(k - 1, C) + c - 1] : 0ull, rule.floor[c]);
+            if (M == BINARY && !ctrl[ctrl_words<M>(C).cnt]) t = ~0ull;      // no positive voxel: nothing
+        }
+        thr[c] = t;
+        if (M != BINARY && stats && blockIdx.x == 0 && c < C) {
+            const Ctrl w = ctrl_words<CLASSES_STATS>(C);
+            stats[c * 3] = c ? (long long)ctrl[w.cnt + c - 1] : 0;
+            stats[c * 3 + 1] = c ? (long long)ctrl[w.vox + c - 1] : 0;
+        }
+    }
+    __syncthreads();
+    const View g = geo.view();
+    int kc = 0, ka = 0;                           // class and area of a kept root this thread holds
+    geo.write_nodes(g, [&](int i, auto value_off, long at) {
+        const int p = parent[i];
+        int o = 0;
+        if (p >= 0) {
+            const int cv = M == BINARY ? 1 : class_of(g.v[value_off()], C);
+            if (cv) {
+                const int r = find_plain(parent, p), ar = area[r];
+                if (root_key(r, ar) >= thr[cv]) {
+                    o = cv;
+                    if (r == i) { kc = cv; ka = ar; }
+                }
+            }
+        }
+        out[at] = (unsigned char)o;
+    });
+    if (M != BINARY && stats && __ballot(kc != 0)) {
+        for (int cc = 1; cc < C; ++cc) {
+            int s = kc == cc ? ka : 0;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+            if ((threadIdx.x & 63) == 0 && s)
+                atomicAdd(reinterpret_cast<unsigned long long*>(stats + cc * 3 + 2), (unsigned long long)s);
+        }
+    }
+}
+
+// ---- hole filling (aide_fill_holes3d; the single volume) ----
+// Launches 1 - 3 under Background<T>: the sets are the face-connected blobs of the voxels that are exactly 0 (inside the slices
+// along `cut` when there is one).  One 32-bit word per root, cleared by a memset, records what the blob touches:
+//   flag   every background voxel ORs into word[find(i)]: bit 0 for a neighbour outside the volume (a face of the volume, or
+//          an edge of the slice: the cut axis has no neighbours) or one holding a value outside 0 .. C - 1, bit c for a
+//          neighbour of class c.  BINARY (C = 0): bit 0 only, no neighbour is read.  Bits are only ever added, so a word that
+//          already shows them needs no atomic
+//   write  a stored class keeps its value (BINARY: 1), a value outside 0 .. C - 1 gives 0, a background voxel gets c where its
+//          root's word is exactly the one bit c >= 1 (BINARY: 1 where bit 0 is clear).  stats[c] += (1, area) at the root of a
+//          filled blob, summed over the wave first
+template <typename T>
+__global__ __launch_bounds__(256) void holes_flag_kernel(Strided geo, Background<T> bg, const int* __restrict__ parent, int C,
+                                                         unsigned* __restrict__ word) {
+    const View g = geo.view();
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (unsigned)(g.d0 * g.d1 * g.d2)) return;
+    const int i = (int)u, p = parent[i];
+    if (p < 0) return;
+    const int plane = g.d1 * g.d2, i0 = i / plane, rem = i - i0 * plane, i1 = rem / g.d2;
+    const int x[3] = {i0, i1, rem - i1 * g.d2}, d[3] = {g.d0, g.d1, g.d2};
+    const long st[3] = {g.s0, g.s1, g.s2}, off = g.off(x[0], x[1], x[2]);
+    unsigned bits = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!bg.joins(a)) continue;
+#pragma unroll
+        for (int sg = -1; sg <= 1; sg += 2) {
+            const int y = x[a] + sg;
+            if (y < 0 || y >= d[a]) { bits |= 1u; continue; }
+            if (C) {
+                const long long nv = (long long)bg.raw(g, off + sg * st[a]);
+                if (nv != 0) bits |= 1u << class_of(nv, C);       // (out of range: class 0, bit 0)
+            }
+        }
+    }
+    if (!bits) return;
+    // A plain load: it may return an older value of the word, which holds a subset of the bits it holds now.  The atomic is
+    // skipped where that already shows this thread's bits, or a word that no further bit can change the fate of (bit 0, or two
+    // bits): the large open blobs stop drawing atomics -- and loads of one L2 line -- early.  What write reads of a word (bit 0,
+    // exactly one bit c) is the same under every schedule
+    unsigned* wp = word + find_plain(parent, p);
+    const unsigned w = *wp;
+    if (!(w & 1u) && !(w & (w - 1u)) && (w & bits) != bits) atomicOr(wp, bits);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void holes_write_kernel(Strided geo, Background<T> bg, const int* __restrict__ parent,
+                                                          const int* __restrict__ area, int C, const unsigned* __restrict__ word,
+                                                          unsigned char* __restrict__ out, long long* __restrict__ stats) {
+    const View g = geo.view();
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    int fc = 0, fa = 0;                           // class and area of a filled blob whose root this thread holds
+    if (u < (unsigned)(g.d0 * g.d1 * g.d2)) {
+        const int i = (int)u, plane = g.d1 * g.d2, i0 = i / plane, rem = i - i0 * plane, i1 = rem / g.d2;
+        const long long v = (long long)bg.raw(g, g.off(i0, i1, rem - i1 * g.d2));
+        int o;
+        if (v != 0) {
+            o = C ? class_of(v, C) : 1;
+        } else {
+            const int r = find_plain(parent, parent[i]);
+            const unsigned w = word[r];
+            o = C ? ((w > 1u && !(w & (w - 1u))) ? __ffs((int)w) - 1 : 0) : !(w & 1u);
+            if (o && r == i) { fc = o; fa = area[i]; }
+        }
+        out[u] = (unsigned char)o;
+    }
+    if (stats && __ballot(fc != 0)) {
+        const int rows = C ? C : 2;
+        for (int cc = 1; cc < rows; ++cc) {
+            int h = fc == cc, s = fc == cc ? fa : 0;
+#pragma unroll
+            for (int dd = 32; dd > 0; dd >>= 1) { h += __shfl_xor(h, dd); s += __shfl_xor(s, dd); }
+            if ((threadIdx.x & 63) == 0 && h) {
+                atomicAdd(reinterpret_cast<unsigned long long*>(stats + cc * 2), (unsigned long long)h);
+                atomicAdd(reinterpret_cast<unsigned long long*>(stats + cc * 2 + 1), (unsigned long long)s);
+            }
+        }
+    }
 }
 
 // ---- confusion sums: out[0..3] = N, sum P*T, sum P, sum T (int64, order-independent atomics) ----
@@ -613,6 +820,16 @@ Ragged make_ragged(const long long* v, const long long* slice_start, int64_t K, 
     return geo;
 }
 
+// launches 1 - 3 under a connectivity predicate: every node gets a root, every root its area
+template <class G, class P>
+void label_launch(const G& geo, const P& pred, const Grids& gr, double bytes, int* parent, int* area, unsigned long long* ctrl,
+                  hipStream_t stream) {
+    const dim3 block(256);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, (lcc_local_kernel<G, P>), gr.tile, block, 0, stream, geo, pred, parent, area, ctrl);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_border_kernel<G, P>), gr.tile, block, 0, stream, geo, pred, parent);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel<G>, gr.count, block, 0, stream, geo, parent, area);
+}
+
 // the five launches over n nodes and K cases; C = 0: BINARY, else the per-class form with one memset in front
 template <class G>
 int lcc_launch(const G& geo, const Grids& gr, int n, int64_t K, int C, unsigned char* out, long long* stats, void* ws,
@@ -631,9 +848,7 @@ int lcc_launch(const G& geo, const Grids& gr, int n, int64_t K, int C, unsigned 
         if (e != hipSuccess) return (int)e;
     }
     const double bytes = 29.0 * n;   // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, select 4, write 4 + 1
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, bytes, lcc_local_kernel<G>, gr.tile, block, 0, stream, geo, parent, area, ctrl);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_border_kernel<G>, gr.tile, block, 0, stream, geo, parent);
-    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lcc_count_kernel<G>, gr.count, block, 0, stream, geo, parent, area);
+    label_launch(geo, Equal{}, gr, bytes, parent, area, ctrl, stream);
     if (!C)
         AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<G, BINARY>), gr.select, block, 0, stream, geo, cparent, carea, C, ctrl);
     else if (stats)
@@ -647,9 +862,120 @@ int lcc_launch(const G& geo, const Grids& gr, int n, int64_t K, int C, unsigned 
     return aide_launch_status();
 }
 
+// the workspace of the single-volume forms below: parent[n], area[n], then, 16-byte aligned, the control words
+struct Carved {
+    int *parent, *area;
+    unsigned long long* ctrl;
+};
+Carved carve(void* ws, int n) {
+    int* parent = static_cast<int*>(ws);
+    return Carved{parent, parent + n, reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(parent + 2 * (size_t)n) + 15) & ~static_cast<uintptr_t>(15))};
+}
+
+// k largest with a floor: memset(s), launches 1 - 3, `passes` select passes, write; C = 0: BINARY
+int kc_launch(const Strided& geo, const Grids& gr, int n, int C, const Rule& rule, int passes, unsigned char* out,
+              long long* stats, void* ws, hipStream_t stream) {
+    const Carved w = carve(ws, n);
+    const int* cparent = w.parent;
+    const int* carea = w.area;
+    const unsigned long long* cctrl = w.ctrl;
+    const dim3 block(256);
+    hipError_t e = hipMemsetAsync(w.ctrl, 0, KC_WORDS * sizeof(unsigned long long), stream);
+    if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, (size_t)(3 * C) * sizeof(long long), stream);
+    if (e != hipSuccess) return (int)e;
+    label_launch(geo, Equal{}, gr, (25.0 + 4.0 * passes) * n, w.parent, w.area, w.ctrl, stream);
+    if (!C)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<Strided, BINARY>), gr.select, block, 0, stream, geo, cparent, carea, C, w.ctrl);
+    else if (stats)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<Strided, CLASSES_STATS>), gr.select, block, 0, stream, geo, cparent, carea, C, w.ctrl);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (lcc_select_kernel<Strided, CLASSES>), gr.select, block, 0, stream, geo, cparent, carea, C, w.ctrl);
+    for (int pass = 1; pass < passes; ++pass) {
+        if (!C)
+            AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (kc_next_kernel<Strided, BINARY>), gr.select, block, 0, stream, geo, cparent, carea, C, pass, w.ctrl);
+        else
+            AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, (kc_next_kernel<Strided, CLASSES>), gr.select, block, 0, stream, geo, cparent, carea, C, pass, w.ctrl);
+    }
+    if (!C)
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, kc_write_kernel<BINARY>, gr.write, block, 0, stream, geo, cparent, carea, C, rule, cctrl, out, stats);
+    else
+        AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, kc_write_kernel<CLASSES>, gr.write, block, 0, stream, geo, cparent, carea, C, rule, cctrl, out, stats);
+    return aide_launch_status();
+}
+
+// hole filling: the root words live behind the two control words launch 1 clears.  memset(s), launches 1 - 3 on the
+// background, flag, write
+template <typename T>
+int holes_launch(const Strided& geo, const Grids& gr, int n, int C, int cut, unsigned char* out, long long* stats, void* ws,
+                 hipStream_t stream) {
+    const Carved w = carve(ws, n);
+    unsigned* word = reinterpret_cast<unsigned*>(w.ctrl + 2);
+    const int* cparent = w.parent;
+    const int* carea = w.area;
+    const unsigned* cword = word;
+    const dim3 block(256);
+    hipError_t e = hipMemsetAsync(word, 0, (size_t)n * sizeof(unsigned), stream);
+    if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, (size_t)(2 * (C ? C : 2)) * sizeof(long long), stream);
+    if (e != hipSuccess) return (int)e;
+    const Background<T> bg{cut};
+    label_launch(geo, bg, gr, (30.0 + 2.0 * sizeof(T)) * n, w.parent, w.area, w.ctrl, stream);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, holes_flag_kernel<T>, gr.write, block, 0, stream, geo, bg, cparent, C, word);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, holes_write_kernel<T>, gr.write, block, 0, stream, geo, bg, cparent, carea, C, cword, out, stats);
+    return aide_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t aide_components3d_ws_bytes(int64_t nvox) { return ws_bytes(nvox, 1, KC_WORDS); }
+
+int aide_keep_components3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                           int num_classes, const int* top_k, const long long* min_voxels, unsigned char* out, long long* stats,
+                           void* ws, hipStream_t stream) {
+    if ((num_classes != 0 && !classes_ok(num_classes)) || !dims_ok(d0, d1, d2) || !top_k || !min_voxels) return AIDE_ERR_ARG;
+    if (stats && !num_classes) return AIDE_ERR_ARG;
+    Rule rule = {};
+    int passes = 1;
+    for (int c = 1; c < (num_classes ? num_classes : 2); ++c) {
+        if (top_k[c] < 0 || top_k[c] > MAXK || min_voxels[c] < 1) return AIDE_ERR_ARG;
+        rule.k[c] = top_k[c];
+        rule.floor[c] = (unsigned long long)std::min(min_voxels[c], 1ll << 31) << 32;   // (no blob has 2^31 voxels)
+        passes = std::max(passes, top_k[c]);
+    }
+    const int n = (int)(d0 * d1 * d2);
+    if (n == 0) {
+        if (!stats) return 0;
+        return (int)hipMemsetAsync(stats, 0, (size_t)(3 * num_classes) * sizeof(long long), stream);
+    }
+    if (!v || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    Grids gr;
+    const Strided geo = make_strided(v, d0, d1, d2, s0, s1, s2, gr);
+    return kc_launch(geo, gr, n, num_classes, rule, passes, out, stats, ws, stream);
+}
+
+size_t aide_fill_holes3d_ws_bytes(int64_t nvox) {
+    const size_t base = ws_bytes(nvox, 1, 2);
+    return base ? base + (size_t)nvox * sizeof(unsigned) : 0;
+}
+
+int aide_fill_holes3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                      int num_classes, int slice_axis, unsigned char* out, long long* stats, void* ws, hipStream_t stream) {
+    if ((num_classes != 0 && !classes_ok(num_classes)) || !dims_ok(d0, d1, d2) || (v_u8 != 0 && v_u8 != 1) || slice_axis < -1 ||
+        slice_axis > 2)
+        return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    if (n == 0) {
+        if (!stats) return 0;
+        return (int)hipMemsetAsync(stats, 0, (size_t)(2 * (num_classes ? num_classes : 2)) * sizeof(long long), stream);
+    }
+    if (!v || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    Grids gr;
+    const Strided geo = make_strided(static_cast<const long long*>(v), d0, d1, d2, s0, s1, s2, gr);
+    if (v_u8) return holes_launch<unsigned char>(geo, gr, n, num_classes, slice_axis, out, stats, ws, stream);
+    return holes_launch<long long>(geo, gr, n, num_classes, slice_axis, out, stats, ws, stream);
+}
 
 size_t aide_lcc3d_ws_bytes(int64_t nvox) { return ws_bytes(nvox, 1, 2); }
 

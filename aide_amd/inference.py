@@ -60,6 +60,9 @@ def predict_labels(net, *modal_inputs, **kw):
     return torch.cat(out, 0) if len(out) > 1 else out[0]
 
 
+_UNSET = object()
+
+
 def predict_case(net, *modal_inputs, **kw):
     """The reference's `generatedtarget`: numpy int64 [H,W,S] (slices stacked on the last axis, :267).
     keep_largest=True: its largest connected component (:268), uint8, filtered on the device before anything leaves it.
@@ -67,11 +70,20 @@ def predict_case(net, *modal_inputs, **kw):
     uint8 class values, for multi-organ networks.
     numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered).
     views=...: the voted labels of `predict_labels(..., views=...)` (`net` may be a list of networks); probs=True then returns
-    (volume, mean probabilities [S,C,H,W]) -- the probabilities are the vote's, before any filter."""
+    (volume, mean probabilities [S,C,H,W]) -- the probabilities are the vote's, before any filter.
+    top_k= / min_voxels=: the filter `keep_largest` selects becomes `keep_components` with them (True: one slot; 'per_class':
+    one per class, sequences allowed); TypeError when keep_largest is False.  fill_holes=True: `fill_holes` after the filter, on
+    its uint8 output, binary or per class as the filter is (keep_largest=False: binary unless num_classes is given), along
+    slice_axis= when given (2 is the slice axis of the [H,W,S] volume).  With all four at their defaults every call takes the
+    path it took before."""
     keep_largest = kw.pop('keep_largest', False)
     want_probs = kw.pop('probs', False)
     num_classes = kw.pop('num_classes', None)
     as_numpy = kw.pop('numpy', True)
+    top_k = kw.pop('top_k', _UNSET)               # (None is a value of its own: every blob that meets min_voxels)
+    min_voxels = kw.pop('min_voxels', _UNSET)
+    fill = kw.pop('fill_holes', False)
+    slice_axis = kw.pop('slice_axis', None)
     per_class = isinstance(keep_largest, str)
     if per_class:
         if keep_largest != 'per_class':
@@ -79,8 +91,15 @@ def predict_case(net, *modal_inputs, **kw):
         if num_classes is None:
             raise TypeError("predict_case: keep_largest='per_class' needs num_classes")
         num_classes = _num_classes(num_classes, 'predict_case')
-    elif num_classes is not None:
-        raise TypeError("predict_case: num_classes goes with keep_largest='per_class'")
+    elif num_classes is not None and (keep_largest or not fill):
+        raise TypeError("predict_case: num_classes goes with keep_largest='per_class' (or with fill_holes and no filter)")
+    ranked = top_k is not _UNSET or min_voxels is not _UNSET
+    if ranked and not keep_largest:
+        raise TypeError('predict_case: top_k / min_voxels go with keep_largest')
+    if fill not in (False, True):
+        raise ValueError('predict_case: fill_holes must be False or True, got %r' % (fill,))
+    if slice_axis is not None and not fill:
+        raise TypeError('predict_case: slice_axis goes with fill_holes=True')
     pr = None
     if want_probs:
         views = kw.pop('views', None)
@@ -91,10 +110,15 @@ def predict_case(net, *modal_inputs, **kw):
         vol = vol.permute(1, 2, 0)
     else:
         vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
-    if per_class:
+    if ranked:
+        vol = keep_components(vol, 1 if top_k is _UNSET else top_k, 1 if min_voxels is _UNSET else min_voxels,
+                              num_classes if per_class else None)
+    elif per_class:
         vol = keep_largest_per_class(vol, num_classes)
     elif keep_largest:
         vol = keep_largest_connected_components(vol)
+    if fill:
+        vol = fill_holes(vol, num_classes, slice_axis)
     if not as_numpy:
         return vol if pr is None else (vol, pr)
     vol = vol.contiguous().cpu().numpy()
@@ -236,6 +260,196 @@ def _keep_largest_classes_device(mask, c, stats):
     check(lib.aide_keep_largest_cc3d_classes(ptr(mask), *mask.shape, *mask.stride(), c, ptr(out), ptr(st), ptr(ws),
                                              stream_ptr()), 'keep_largest_cc3d_classes')
     return out, st
+
+
+# ---- case post-processing: the k largest blobs with a size floor, hole filling ------------------------------------------
+MAX_TOP_K = 8
+
+
+def _post_classes(num_classes, what):
+    if num_classes is None:
+        return None
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 2 <= num_classes <= 8:
+        raise ValueError('%s: num_classes %r, None or 2 .. 8 are supported' % (what, num_classes))
+    return int(num_classes)
+
+
+def _per_class(value, c, name, check):
+    """`value` (one entry, or with num_classes=c a sequence of c entries, entry 0 ignored) -> list of 8 checked entries"""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if c is None or len(value) != c:
+            raise ValueError('keep_components: a sequence for %s needs num_classes and one entry per class value, got %r'
+                             % (name, value))
+        vals = [check(v) for v in list(value)[1:]]
+    else:
+        vals = [check(value)] * ((c or 2) - 1)
+    return [0] + vals + [vals[0]] * (8 - 1 - len(vals))
+
+
+def _top_k(k):
+    if k is None:
+        return 0
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_TOP_K:
+        raise ValueError('keep_components: top_k %r, None or 1 .. %d are supported' % (k, MAX_TOP_K))
+    return int(k)
+
+
+def _min_voxels(m):
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
+        raise ValueError('keep_components: min_voxels %r, an integer >= 1 is expected' % (m,))
+    return min(int(m), 2 ** 31)
+
+
+def _blobs_of(mask, v):
+    """(labels, areas, first raster index) of the face-connected blobs of mask == v, one row per blob"""
+    from scipy import ndimage
+    blobs, count = ndimage.label(mask == v)
+    flat = blobs.reshape(-1)
+    area = np.bincount(flat, minlength=count + 1)[1:]
+    first = np.full(count + 1, flat.size, dtype=np.int64)
+    idx = np.flatnonzero(flat)
+    np.minimum.at(first, flat[idx], idx)
+    return blobs, area, first[1:]
+
+
+def _keep_components_host(mask, c, ks, ms):
+    """the host statement of aide_keep_components3d: scipy.ndimage.label once per value"""
+    out = np.zeros(mask.shape, dtype=np.uint8)
+    st = np.zeros((c or 2, 3), dtype=np.int64)
+    if mask.size == 0 or (c is None and mask.max() <= 0):
+        return out, st
+    slots = [(v, [v]) for v in range(1, c)] if c else [(1, [v for v in np.unique(mask).tolist() if v != 0])]
+    for cls, values in slots:
+        found = []                                # (-area, first voxel, index into labelled, blob id)
+        labelled = []
+        for v in values:
+            blobs, area, first = _blobs_of(mask, v)
+            labelled.append((blobs, len(area)))
+            found += [(-int(a), int(f), len(labelled) - 1, b + 1) for b, (a, f) in enumerate(zip(area, first))]
+        found.sort()
+        kept = [f for f in (found[:ks[cls]] if ks[cls] else found) if -f[0] >= ms[cls]]
+        for j, (blobs, count) in enumerate(labelled):
+            lut = np.zeros(count + 1, bool)
+            lut[[f[3] for f in kept if f[2] == j]] = True
+            out[lut[blobs]] = cls
+        st[cls] = len(found), -sum(f[0] for f in found), -sum(f[0] for f in kept)
+    return out, st
+
+
+def keep_components(volume, top_k=1, min_voxels=1, num_classes=None, stats=False):
+    """The component rule of `keep_largest_connected_components` / `keep_largest_per_class` with a rank and a size floor.
+    Face neighbours of equal value are connected.  num_classes=None: one slot over all non-zero values, 1 is written (nothing
+    when no value is positive, as the binary filter).  num_classes=C (2 .. 8): one slot per class value 1 .. C - 1, the class
+    value is written; a value outside 1 .. C - 1 belongs to no class.  Inside a slot larger blobs come first and a tie goes to
+    the blob whose first voxel has the lower raster index of the logical volume; kept are the first `top_k` blobs of that
+    order (1 .. 8, or None for all), and of those the ones with at least `min_voxels` (>= 1) voxels.  With num_classes=C both
+    may be sequences of C entries, one per class value, entry 0 ignored: top_k=(0, 1, 2) keeps one liver and two kidneys.
+    Anything else raises ValueError before a launch.  top_k=1, min_voxels=1 is the two existing filters byte for byte.
+    stats=True (with num_classes=C; TypeError without): also int64 [C, 3], row c = (blobs of class c, voxels of class c, voxels
+    kept), row 0 zeros.  HIP integer tensor of any strides: `aide_keep_components3d`, 4 + max(1, top_k) launches, asynchronous,
+    HIP tensors returned.  numpy array or CPU tensor: scipy.ndimage.label once per value, numpy arrays returned."""
+    c = _post_classes(num_classes, 'keep_components')
+    if stats and c is None:
+        raise TypeError('keep_components: stats needs num_classes')
+    ks = _per_class(top_k, c, 'top_k', _top_k)
+    ms = _per_class(min_voxels, c, 'min_voxels', _min_voxels)
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        import ctypes
+        _lcc_args(volume)
+        v = volume.detach()
+        if v.dtype != torch.int64:
+            v = v.to(torch.int64)
+        out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
+        st = torch.empty(c, 3, device=v.device, dtype=torch.int64) if stats else None
+        if v.numel() == 0:
+            return (out, st.zero_()) if stats else out
+        ws = torch.empty(lib.aide_components3d_ws_bytes(v.numel()), device=v.device, dtype=torch.uint8)
+        check(lib.aide_keep_components3d(ptr(v), *v.shape, *v.stride(), c or 0, (ctypes.c_int * 8)(*ks),
+                                         (ctypes.c_longlong * 8)(*ms), ptr(out), ptr(st), ptr(ws), stream_ptr()),
+              'keep_components3d')
+        return (out, st) if stats else out
+    if isinstance(volume, torch.Tensor):
+        volume = volume.detach().numpy()
+    out, st = _keep_components_host(np.asarray(volume), c, ks, ms)
+    return (out, st) if stats else out
+
+
+def _fill_holes_host(vol, c, axis):
+    """the host statement of aide_fill_holes3d: scipy.ndimage.label of the background (no links along `axis`), then per blob
+    the set of things it touches"""
+    from scipy import ndimage
+    rows = c or 2
+    st = np.zeros((rows, 2), dtype=np.int64)
+    cls = np.where((vol >= 1) & (vol < c), vol, 0).astype(np.uint8) if c else (vol != 0).astype(np.uint8)
+    if vol.size == 0:
+        return cls, st
+    link = ndimage.generate_binary_structure(3, 1)
+    axes = [a for a in range(3) if a != axis]
+    if axis is not None:
+        link = link.copy()
+        index = [1, 1, 1]
+        for end in (0, 2):
+            index[axis] = end
+            link[tuple(index)] = False
+    blobs, count = ndimage.label(vol == 0, structure=link)
+    touch = np.zeros(count + 1, np.int64)         # bit 0: open or next to an out-of-range value, bit c: next to class c
+    for a in axes:
+        for end in (0, -1):
+            touch[np.unique(np.take(blobs, end, axis=a))] |= 1
+        lo, hi = [slice(None)] * 3, [slice(None)] * 3
+        lo[a], hi[a] = slice(0, -1), slice(1, None)
+        for here, there in ((tuple(lo), tuple(hi)), (tuple(hi), tuple(lo))):
+            sel = (blobs[here] != 0) & (vol[there] != 0)
+            np.bitwise_or.at(touch, blobs[here][sel], np.int64(1) << cls[there][sel].astype(np.int64) if c else 0)
+    touch[0] = 1
+    single = (touch & 1) == 0 if not c else (touch > 1) & (touch & (touch - 1) == 0)
+    fill = np.zeros(count + 1, np.uint8)
+    fill[single] = np.log2(touch[single]).astype(np.uint8) if c else 1
+    out = np.where(blobs != 0, fill[blobs], cls).astype(np.uint8)
+    area = np.bincount(blobs.reshape(-1), minlength=count + 1)
+    for k in range(1, rows):
+        st[k] = int((fill == k).sum()), int(area[fill == k].sum())
+    return out, st
+
+
+def fill_holes(volume, num_classes=None, slice_axis=None, stats=False):
+    """Fill the enclosed cavities of a label volume.  Background is the voxels with value exactly 0; a hole is a face-connected
+    blob of background with no voxel on a face of the volume.  slice_axis=a (0, 1 or 2): connectivity is restricted to the
+    2-D slices along axis a and "face of the volume" reads "edge of the slice", the usual rule for anisotropic stacks
+    (`predict_case`'s [H,W,S] volumes: slice_axis=2).
+    num_classes=None: uint8, 1 where volume != 0 or the voxel lies in a hole: `scipy.ndimage.binary_fill_holes(volume != 0)`,
+    applied per slice with a slice axis.  num_classes=C (2 .. 8): a voxel of class 1 .. C - 1 keeps its value, a value outside
+    0 .. C - 1 is written as 0, and a hole is filled with class c if and only if every non-background face neighbour of the
+    hole has value c, 1 <= c <= C - 1: a hole that touches two classes, or an out-of-range value, stays 0.  C = 2 on a {0, 1}
+    volume is the binary result.  ValueError for any other num_classes or slice_axis.
+    stats=True: also int64 [C, 2] (binary: [2, 2], row 1), row c = (holes filled with c, voxels filled with c), row 0 zeros.
+    HIP tensor, int64 or uint8 (other integer types are widened), any strides: `aide_fill_holes3d`, five launches, asynchronous,
+    HIP tensors returned.  numpy array or CPU tensor: scipy.ndimage.label of the background, numpy arrays returned."""
+    c = _post_classes(num_classes, 'fill_holes')
+    if slice_axis is not None and (isinstance(slice_axis, bool) or not isinstance(slice_axis, (int, np.integer))
+                                   or not 0 <= slice_axis <= 2):
+        raise ValueError('fill_holes: slice_axis %r, None, 0, 1 or 2 are supported' % (slice_axis,))
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        _lcc_args(volume)
+        v = volume.detach()
+        if v.dtype not in (torch.int64, torch.uint8):
+            v = v.to(torch.int64)
+        out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
+        st = torch.empty(c or 2, 2, device=v.device, dtype=torch.int64) if stats else None
+        if v.numel() == 0:
+            return (out, st.zero_()) if stats else out
+        ws = torch.empty(lib.aide_fill_holes3d_ws_bytes(v.numel()), device=v.device, dtype=torch.uint8)
+        check(lib.aide_fill_holes3d(ptr(v), int(v.dtype == torch.uint8), *v.shape, *v.stride(), c or 0,
+                                    -1 if slice_axis is None else int(slice_axis), ptr(out), ptr(st), ptr(ws), stream_ptr()),
+              'fill_holes3d')
+        return (out, st) if stats else out
+    if isinstance(volume, torch.Tensor):
+        volume = volume.detach().numpy()
+    volume = np.asarray(volume)
+    if volume.ndim != 3:
+        raise RuntimeError('fill_holes: a 3-D volume is expected, got %d dims' % volume.ndim)
+    out, st = _fill_holes_host(volume, c, None if slice_axis is None else int(slice_axis))
+    return (out, st) if stats else out
 
 
 def _confusion_args(pred, target):

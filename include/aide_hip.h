@@ -528,6 +528,39 @@ int aide_keep_largest_cc3d_classes(const long long* v, int64_t d0, int64_t d1, i
                                    int64_t s0, int64_t s1, int64_t s2, int num_classes,
                                    unsigned char* out, long long* stats /* NULL or [C][3] */,
                                    void* ws, aide_stream_t stream);
+/* ---- case post-processing: the k largest blobs with a size floor, hole filling (the single volume) ---- */
+/* workspace of aide_keep_components3d (16-byte aligned); 0 for nvox >= 2^31 */
+size_t aide_components3d_ws_bytes(int64_t nvox);
+/* The component rule of the two filters above with a rank and a size floor.  num_classes = 0: one slot over all non-zero
+ * values, 1 written (nothing when no value is positive, as aide_keep_largest_cc3d); num_classes = C in 2 .. 8: one slot per
+ * class value 1 .. C - 1, the class written.  Inside a slot blobs are ordered by voxel count, larger first, ties to the blob
+ * whose first voxel comes first in raster order (the key (area << 32) | (0x7fffffff - root)); kept are the first top_k[c]
+ * of that order (0: all of them), and of those the ones with at least min_voxels[c] voxels.  top_k and min_voxels are HOST
+ * arrays of 8 entries read before the call returns, indexed by class value (num_classes = 0: entry 1; entry 0 is ignored);
+ * top_k[c] in 0 .. 8, min_voxels[c] >= 1.  top_k = 1, min_voxels = 1 gives the bytes (and stats) of the two filters above.
+ * stats: NULL, or with num_classes = C [C][3] int64: row c = {blobs of class c, voxels of class c, voxels kept}, row 0 zeros.
+ * Launches: 4 + max(1, max top_k) and one or two memsets; integer only, no host read, the same bytes from call to call.
+ * AIDE_ERR_ARG before any launch for num_classes outside {0, 2 .. 8}, an entry out of range, null top_k / min_voxels, stats with
+ * num_classes = 0, d0 * d1 * d2 >= 2^31, a null v / out / ws or a misaligned ws; an empty volume launches nothing. */
+int aide_keep_components3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                           int num_classes, const int* top_k /* host [8] */, const long long* min_voxels /* host [8] */,
+                           unsigned char* out, long long* stats /* NULL or [C][3] */, void* ws, aide_stream_t stream);
+/* workspace of aide_fill_holes3d (16-byte aligned); 0 for nvox >= 2^31 */
+size_t aide_fill_holes3d_ws_bytes(int64_t nvox);
+/* Background: the voxels whose value is exactly 0 (v is int64, v_u8 = 0, or uint8, v_u8 = 1, with element strides).  A hole: a
+ * face-connected blob of background with no voxel on a face of the volume.  slice_axis = a in 0 .. 2 (-1: none): connectivity
+ * is restricted to the 2-D slices along logical axis a and "face of the volume" reads "edge of the slice".
+ * num_classes = 0: out = 1 where v != 0 or the voxel lies in a hole (scipy.ndimage.binary_fill_holes(v != 0), per slice with a
+ * slice axis).  num_classes = C in 2 .. 8: a class value 1 .. C - 1 is kept, a value outside 0 .. C - 1 gives 0, and a hole gets
+ * class c if and only if every non-background face neighbour of the hole holds c, 1 <= c <= C - 1: a hole between two classes
+ * or next to an out-of-range value stays 0.
+ * stats: NULL, or [max(C, 2)][2] int64: row c = {holes filled with c, voxels filled with c}, row 0 zeros (num_classes = 0: row 1).
+ * The labelling launches of the filters on the background, one launch that ORs what each blob touches into a word per root,
+ * one that writes; one or two memsets; integer atomics only, no host read, the same bytes from call to call.  AIDE_ERR_ARG
+ * before any launch as for aide_keep_components3d, and for v_u8 outside {0, 1} or slice_axis outside -1 .. 2. */
+int aide_fill_holes3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                      int num_classes, int slice_axis, unsigned char* out, long long* stats /* NULL or [max(C, 2)][2] */,
+                      void* ws, aide_stream_t stream);
 /* out[4] (int64) = {N, sum p*t, sum p, sum t} over the logical volume; p / t are int64 (x_u8 = 0) or uint8 (x_u8 = 1)
  * with element strides.  TP = out[1], FP = out[2] - out[1], FN = out[3] - out[1], TN = N - out[2] - out[3] + out[1] */
 int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
