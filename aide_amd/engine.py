@@ -60,7 +60,7 @@ class Graph(object):
 
     def conv_bn_relu(self, src, dst, conv, bn, lane=0):
         """lane = 1 marks a chain that is independent of the lane-0 ops next to it (the second encoder of a two-modality
-        net): the forward pass may run it on a second stream (Plan._forward_impl)."""
+        net): the forward pass may run it on a second stream (lane_schedule)."""
         self.ops.append(dict(kind='conv', src=src, dst=dst, conv=conv, bn=bn, lane=lane))
 
     def convT_bn_relu(self, src, dst, conv, bn):
@@ -69,7 +69,7 @@ class Graph(object):
     def pool(self, src, dst, lane_split=None):
         """lane_split = c: channels [0, c) of src were written by lane-0 ops, [c, C) by the lane-1 chain.  Max-pooling is per
         channel, so the forward pass may pool each part on the stream that produced it: lane 1 then runs from level to level
-        without waiting for lane 0 (Plan._forward_impl); the backward pass treats the op as one."""
+        without waiting for lane 0 (lane_schedule); the backward pass treats the op as one."""
         self.ops.append(dict(kind='pool', src=src, dst=dst, lane_split=lane_split))
 
     def upsample(self, src, dst):
@@ -110,7 +110,7 @@ class EngineConfig(object):
         fold_eval_bn=True,          # eval-mode BatchNorm + ReLU in the conv epilogue (no pass over the conv output)
         tail_wgrad_main=True,       # the weight gradient of the LAST op of the backward pass on the main stream
         dual_fwd=True,              # lane-1 chains of the forward pass on a second stream
-        free_lane=True,             # lane 1 pools its own channels and runs ahead (no fork / join per level)
+        free_lane=True,             # lane 1 pools its own channels and runs ahead; off: lane_schedule with every pooling whole
         handover_on_kernel=True,    # the dz hand-over event of a layer rides on its BatchNorm backward's last dispatch
         w4_half_tile=True,          # F(4x4) weight gradient also for Co = 32 layers (trailing half tile computed and dropped)
         grouped_bn=True,            # stacked plans: BatchNorm of all groups in one launch sequence
@@ -244,10 +244,14 @@ def _wgrad_extra(st):
     return dict(target_wgs=256) if st.get('wg_target') else {}
 
 
+def _overlap(a, b):
+    """the tensor ranges a and b share a channel"""
+    return a.root is b.root and a.c0 < b.c0 + b.C and b.c0 < a.c0 + a.C
+
+
 def _readers(ops_, t):
     """indices of the ops that read any channel of the tensor range t"""
-    return [i for i, o in enumerate(ops_) if o.get('src') is not None and o['src'].root is t.root
-            and o['src'].c0 < t.c0 + t.C and t.c0 < o['src'].c0 + o['src'].C]
+    return [i for i, o in enumerate(ops_) if o.get('src') is not None and _overlap(o['src'], t)]
 
 
 def _producers(ops_, t):
@@ -433,6 +437,65 @@ def select_fusions(graph, convs, cfg, precision, training, groups, n, h, w):
     return out
 
 
+def gate_step(steps):
+    """index of convs[4], the only conv that ever waits for the side-stream filter packs (Plan._pack_filters); None: <= 4 convs"""
+    convs = [i for i, st in enumerate(steps) if st['kind'] == 'conv']
+    return convs[4] if len(convs) > 4 else None
+
+
+def lane_schedule(steps, dual, free, gate_index):
+    """Where the forward pass launches, forks, joins, records and waits, from kind, src, dst, lane and lane_split of every step
+    alone -> the flat list of actions Plan._forward_impl executes one by one (the contract they keep: DESIGN.md, "Lanes"):
+        ('op', i, lane)            step i as a whole on the main stream (lane 0) or on the lane stream (lane 1)
+        ('pool_half', i, lane)     split pooling i: channels [c, C) of its source on the lane stream (1), [0, c) on the main stream (0)
+        ('fork',)  ('join',)       the lane stream waits for the main stream's work so far / the main stream for the lane's
+        ('record', i)  ('wait', i) step i's event ev_b behind its lane-1 pooling half / the main stream waits for that event
+        ('gate',)                  before step gate_index: the wait for the side stream's filter packs (Plan._pack_filters)
+    dual: the lane = 1 ops (Graph.conv_bn_relu) run on the lane stream beside the lane-0 chain of the same level -- one chain's
+    HBM-bound BatchNorm and launch boundaries under the other's convolutions.  free: a pooling with lane_split = c runs as two
+    launches, each on the stream that produced its channels: lane 1 never waits for lane 0 after the first fork, and lane 0 waits
+    for lane 1 only where it reads lane 1's pooled channels, on the event behind that launch (whole poolings on the main stream: a
+    join + a fork per level, ~35 us of idle time per lane and level).  A gate conv on lane 1 must see the wait too: the gate re-forks."""
+    hit = lambda ranges, ts: any(_overlap(r, t) for r in ranges for t in ts)
+    acts, forked = [], False   # forked: lane 1 has been ordered behind the main stream (since the last event that needs it again)
+    touched = []          # ranges lane-0 ops read or wrote since the last fork
+    b_reads = []          # ranges lane-1 ops read since the last join
+    pend = []             # ranges lane-1 ops wrote since the last join
+    pooled = []           # (range, step) of lane-1 pooling halves the main stream has not waited for yet
+    for i, st in enumerate(steps):
+        if i == gate_index:
+            acts.append(('gate',))
+            forked = False
+        src, dst = st['src'], st.get('dst')
+        c = st.get('lane_split') if (free and forked and st['kind'] == 'pool') else None
+        halves = c and [(1, src.slice(c, src.C - c), dst.slice(c, dst.C - c)), (0, src.slice(0, c), dst.slice(0, c))]
+        for lane, s, d in halves or [(st.get('lane', 0) if dual else 0, src, dst)]:
+            ts = [s] if d is None else [s, d]
+            if lane:
+                if not forked or hit(touched, ts):
+                    acts.append(('fork',))
+                    forked, touched = True, []
+                b_reads.append(s)
+                if c:
+                    pooled.append((d, i))
+                else:
+                    pend.append(d)
+            else:
+                if hit(pend, ts) or hit(b_reads, ts[1:]):       # lane 1 wrote what the op touches, or read what it writes
+                    acts.append(('join',))
+                    pend, b_reads, pooled = [], [], []
+                for e in [e for e in pooled if hit(e[:1], ts)]:
+                    acts.append(('wait', e[1]))
+                    pooled.remove(e)
+                touched += ts
+            acts.append(('pool_half' if c else 'op', i, lane))
+            if c and lane:
+                acts.append(('record', i))
+    if pend or pooled:
+        acts.append(('join',))
+    return acts
+
+
 def _pack_slot(mode, direction):
     """step key of a conv's filter pack of one direction ('f' | 'd'): 'wf' / 'wd' direct kernel, 'uf' / 'ud' the others"""
     return ('u' if mode else 'w') + direction
@@ -506,14 +569,14 @@ class _Cover(object):
 #   mean rstd scale shift fbias  init       executors                    BatchNorm per-channel vectors
 #   stats                        init       _forward_op _bn_apply        the statistics partials (None: stats_parts == 0)
 #   t1 t2 t3 t4 gate stat        init       executors ('sa')             spatial-attention intermediates
-#   ev_b                         init       _forward_impl                split pooling: lane 1's half is pooled
+#   ev_b                         init       _forward_impl                split pooling: lane 1's half is pooled (lane_schedule: 'record', 'wait')
 #   lazy_to, tab_c0              fusions    _forward_op                  reader step whose loader applies this layer's BatchNorm
 #                                                                        + ReLU; first channel of its rows in the reader's in_tab
 #   in_tab                       init       _forward_op                  that reader's [groups, Cin, 2] (scale, shift) table
 #   head_lazy, head_tab          fusions    _forward_op, tests           the head applies this layer's BatchNorm + ReLU; its table
 #   lazy_prod                    fusions    _forward_op _backward_op     head: the head_lazy step under it
 #   pool_out                     fusions    _bn_apply                    pooled slice this layer's BatchNorm forward also writes
-#   fwd_fused                    fusions    _forward_op _forward_impl, tests   pool: written by its producers (pool_out)
+#   fwd_fused                    fusions    _forward_op _forward_impl, tests   pool: written by its producers (pool_out); training plans only
 #   src_grad                     fusions    _backward_op                 None (network input) | dict(accumulate, gaps to zero-fill)
 #   fold_dgrad                   fusions    _backward_op                 split-K dgrad slabs summed by the BatchNorm backward before
 #   pool_fuse                    fusions    _backward_op                 pooled-gradient slice this layer's BatchNorm backward routes
@@ -641,7 +704,7 @@ class Plan(object):
         # data-parallel path needs one of them for RCCL's own stream (aide_amd/distributed.py)
         self.side = _side_stream(device) if (training and groups == 1) else None
         self._convs = self._conv_wslots = None
-        self._gate_conv = None           # the first conv that needs the side-stream filter packs
+        self.gate_index, self._lane_schedules = gate_step(self.steps), {}    # (dual, free) -> lane_schedule(...): both switch at run time
         self._tape_f = self._tape_b = None
         self._coef_key, self._coef_tensors, self._coef_ok, self._coef_next, self._coef_bns = None, None, False, None, []
         self._fp = None
@@ -702,7 +765,7 @@ class Plan(object):
         """Refresh the packed forward/dgrad filters when any master weight changed (tensor._version for
         torch optimizers, PARAM_EPOCH for the fused Adam).  Two launches: the first few (tiny, stage-1)
         filters on the main stream, all the others on the side stream so that the 0.25 ms re-layout runs
-        under the first convolutions; returns the index of the first conv that must wait for it.
+        under the first convolutions; returns the conv that must wait for it (the step at plan.gate_index) or None: no wait.
         Packs another plan of the same engine has already refreshed for these weights (shared buffers) are skipped."""
         convs = self._convs
         if convs is None:
@@ -746,7 +809,6 @@ class Plan(object):
                 self._pack_tabs.clear()
             self._pack_tabs[(ptrs, fresh)] = cached
         first, rest, gate = cached
-        self._gate_conv = gate
 
         def launch(tabs):
             for mode in PACK_ORDER:
@@ -857,109 +919,46 @@ class Plan(object):
         return out
 
     def _forward_impl(self, inputs, out, gate, tape):
-        n = self.N
         if not self.training and (tape is not None or not self._coef_ok):
             # eval-mode coefficients of every BatchNorm, once per change of the parameters / running statistics (a replayed
             # tape skips these entries while they are fresh)
             for st in self.steps:
                 if st['kind'] in ('conv', 'convT'):
                     ops.bn_eval_fold(st['bn'], st['conv'].bias, st['scale'], st['shift'], st['fbias'])
-        # Two lanes: the ops a graph marks lane = 1 (the second encoder of a two-modality net: an independent conv -> BN ->
-        # conv -> BN chain per level) run on a second stream, beside the lane-0 chain of the same level -- one chain's
-        # HBM-bound BatchNorm and launch boundaries under the other's convolutions.  Fork: lane 1 waits for everything
-        # enqueued on the main stream so far; join: before the first main-stream op that touches channels lane 1 wrote.
+        # what runs where, and every fork, join, record and wait, is lane_schedule's; the loop below holds no dependency state
         dual = self.lane_b is not None and self.cfg.dual_fwd and self.profiler is None and self.trace is None
+        key = (dual, dual and self.cfg.free_lane)
+        if key not in self._lane_schedules:
+            self._lane_schedules[key] = lane_schedule(self.steps, key[0], key[1], self.gate_index)
         mp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         bp = ctypes.c_void_p(self.lane_b.cuda_stream) if dual else None
-        # Free-running lane 1 (config.free_lane): a pooling op whose source holds lane-0 channels [0, c) and lane-1 channels [c, C)
-        # runs as two launches, each on the stream that produced its channels.  Lane 1 then never waits for lane 0 after the
-        # first fork (its next level reads only what it pooled itself), and lane 0 waits for lane 1 exactly where it reads
-        # lane 1's pooled channels -- on an event recorded right behind that pooling launch, not on lane 1's tail.  (With one
-        # pooling launch per level on the main stream each level cost a join + a fork: ~35 us of idle time per lane and level.)
-        free = dual and self.cfg.free_lane
-        on_b, pend = False, []
-        forked = False        # free: lane 1 has been ordered behind the main stream (since the last event that needs it again)
-        touched = []          # free: ranges lane-0 ops read or wrote since the last fork
-        b_reads = []          # free: ranges lane-1 ops read since the last join
-        pooled = []           # free: (root, c0, C, event) of lane-1 pooling halves the main stream has not waited for yet
-
-        def hit(ranges, t):
-            return any(r[0] is t.root and r[1] < t.c0 + t.C and t.c0 < r[1] + r[2] for r in ranges)
-
-        def overlaps(t):
-            return hit(pend, t)
-
-        def fork_if_needed(srcs, dsts):
-            nonlocal forked
-            if not forked or any(hit(touched, t) for t in srcs + dsts):
+        for a in self._lane_schedules[key]:
+            act, st = a[0], self.steps[a[1]] if len(a) > 1 else None
+            if act == 'op':
+                if self.trace is not None:
+                    self.trace('f', st)
+                with ops.use_stream(bp if a[2] else mp):
+                    self._forward_op(st, inputs, out, *((self.bn_ws_b, self.sk_ws_b) if a[2] else (self.bn_ws, self.sk_ws)))
+            elif act == 'pool_half':
+                if not st['fwd_fused']:           # (else: both halves were written by their producers' BatchNorm kernels)
+                    src, dst, c = st['src'], st['dst'], st['lane_split']
+                    c0, nc = (c, src.C - c) if a[2] else (0, c)
+                    with ops.use_stream(bp if a[2] else mp):
+                        ops.maxpool2x2_fwd(self.view(src.slice(c0, nc), inputs), self.view(dst.slice(c0, nc)))
+            elif act == 'fork':
                 ops.order(self.ev_lane_fork, mp, bp)
-                forked = True
-                del touched[:]
-
-        def main_deps(srcs, dsts):
-            """order the main stream behind whatever lane 1 work the op depends on"""
-            if any(hit(pend, t) for t in srcs + dsts) or any(hit(b_reads, t) for t in dsts):
+            elif act == 'join':
                 ops.order(self.ev_lane_join, bp, mp)
-                del pend[:], b_reads[:], pooled[:]
-            for e in [e for e in pooled if any(hit([e], t) for t in srcs + dsts)]:
-                ops.wait(mp, e[3])
-                pooled.remove(e)
-        for st in self.steps:
-            kind = st['kind']
-            if self.trace is not None:
-                self.trace('f', st)
-            lane = st.get('lane', 0) if dual else 0
-            if kind == 'conv' and st is self._gate_conv:      # (when) the remaining filters were re-packed on the side stream
+            elif act == 'record':
+                ops.record(st['ev_b'], bp)
+            elif act == 'wait':
+                ops.wait(mp, st['ev_b'])
+            elif act == 'gate':                   # (when) the remaining filters were re-packed on the side stream
                 wait = lambda: torch.cuda.current_stream().wait_stream(self.side_fwd)
                 if tape is not None:
                     tape.py(wait, 'gate')
                 if gate is not None:
                     wait()
-                on_b = forked = False         # a gate conv on lane 1 re-forks: its lane must see the wait as well
-            if free:
-                srcs = [st['src']]
-                dsts = [st['dst']] if st.get('dst') is not None else []
-                c = st.get('lane_split') if kind == 'pool' else None
-                if c and forked:
-                    src, dst = st['src'], st['dst']
-                    sa, da, sb, db = src.slice(0, c), dst.slice(0, c), src.slice(c, src.C - c), dst.slice(c, dst.C - c)
-                    fork_if_needed([sb], [db])
-                    fused = bool(st.get('fwd_fused'))      # both halves were written by their producers' BatchNorm kernels
-                    if not fused:
-                        with ops.use_stream(bp):
-                            ops.maxpool2x2_fwd(self.view(sb, inputs), self.view(db))
-                    ops.record(st['ev_b'], bp)
-                    pooled.append((db.root, db.c0, db.C, st['ev_b']))
-                    b_reads.append((sb.root, sb.c0, sb.C))
-                    main_deps([sa], [da])
-                    if not fused:
-                        ops.maxpool2x2_fwd(self.view(sa, inputs), self.view(da))
-                    touched.extend((t.root, t.c0, t.C) for t in (sa, da))
-                elif lane:
-                    fork_if_needed(srcs, dsts)
-                    pend.extend((t.root, t.c0, t.C) for t in dsts)
-                    b_reads.extend((t.root, t.c0, t.C) for t in srcs)
-                    with ops.use_stream(bp):
-                        self._forward_op(st, inputs, out, self.bn_ws_b, self.sk_ws_b)
-                else:
-                    main_deps(srcs, dsts)
-                    touched.extend((t.root, t.c0, t.C) for t in srcs + dsts)
-                    self._forward_op(st, inputs, out, self.bn_ws, self.sk_ws)
-                continue
-            if lane and not on_b:
-                ops.order(self.ev_lane_fork, mp, bp)
-            on_b = bool(lane)
-            if not lane and pend and (overlaps(st['src']) or (st.get('dst') is not None and overlaps(st['dst']))):
-                ops.order(self.ev_lane_join, bp, mp)
-                del pend[:]
-            if lane:
-                pend.append((st['dst'].root, st['dst'].c0, st['dst'].C))
-                with ops.use_stream(bp):
-                    self._forward_op(st, inputs, out, self.bn_ws_b, self.sk_ws_b)
-            else:
-                self._forward_op(st, inputs, out, self.bn_ws, self.sk_ws)
-        if pend or pooled:
-            ops.order(self.ev_lane_join, bp, mp)
         return out
 
     def _forward_op(self, st, inputs, out, bn_ws, sk_ws):
@@ -1012,7 +1011,7 @@ class Plan(object):
             ops.convT2x2_fwd(self.view(st['src'], inputs), conv.weight, conv.bias, st['z'])
             self._bn_apply(st, bn, None, 0, bn_ws, sk_ws)
         elif kind == 'pool':
-            if not (st.get('fwd_fused') and self.training):
+            if not st['fwd_fused']:            # (fwd_fused: select_fusions decides it for training plans only)
                 ops.maxpool2x2_fwd(self.view(st['src'], inputs), self.view(st['dst']))
         elif kind == 'up':
             ops.upsample2x_fwd(self.view(st['src'], inputs), self.view(st['dst']))

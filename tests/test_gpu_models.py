@@ -448,6 +448,34 @@ def test_two_lane_schedules_are_bit_identical(dev):
             assert torch.equal(a, b)
 
 
+def test_tape_recorded_without_a_gate_still_waits_for_later_repacks(dev):
+    """An eval plan whose first forward follows a training forward of the same weights finds every filter pack fresh: its
+    _pack_filters returns no gate while the forward tape is recorded.  The tape must hold the 'gate' entry all the same (the
+    gate's position is a property of the plan, Plan.gate_index): after a weight update the re-layout runs on the side stream
+    again, and the replay has to wait for it."""
+    net, _ = build_pair('fuseunet', False, dev)
+    g = torch.Generator().manual_seed(13)
+    xs = [torch.randn(2, 3, 64, 64, generator=g).to(dev) for _ in range(2)]
+    net.train()
+    net(*xs)
+    net.eval()
+    with torch.no_grad():
+        net(*xs)
+        plan = [p for p in net.engine.plans.values() if not p.training][0]
+        assert plan.gate_index is not None
+        assert [c[2] for c in plan._pack_tabs.values()] == [None], 'the recording forward was meant to find every pack fresh'
+        tape = plan._tape_f
+        assert tape is not None and sum(1 for c in tape.calls if c[0] is None and c[2] == 'gate') == 1
+        for m in net.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                m.weight.mul_(1.03125)
+        gated = net(*xs).clone()          # a replay behind a side-stream re-layout
+        assert plan._tape_f is tape and sorted(c[2] is None for c in plan._pack_tabs.values()) == [False, True]
+        torch.cuda.synchronize()
+        again = net(*xs)                  # the packs are fresh and complete: no gate needed
+        assert plan._tape_f is tape and torch.equal(gated, again)
+
+
 @pytest.mark.parametrize('kind', ['fuseunet', 'unet'])
 def test_pool_backward_inside_batchnorm_is_bit_identical(dev, kind):
     """config.fuse_pool_bwd: the max-pooling backward of every level folded into the BatchNorm backward of the layer(s) it pooled
