@@ -496,6 +496,70 @@ def lane_schedule(steps, dual, free, gate_index):
     return acts
 
 
+def backward_schedule(steps, side, tail_main, on_kernel, batched):
+    """What the backward pass launches, on which stream, and every fork, hand-over, flush point and join, from kind, src_grad,
+    fold_dgrad, plan_d, pool_fuse, head_fuse, dgrad_fused, lazy_prod and bwd_fused of every step alone -> the flat list of actions
+    Plan._backward_run executes one by one (the contract they keep: DESIGN.md, "Backward").  Stream 0 is the main stream, which
+    carries the dependent chain, stream 1 the weight-gradient stream:
+        ('fork',)  ('join',)            stream 1 waits for the main stream's work so far / the main stream for all of stream 1's
+        ('begin', i)  ('end', i)        around the launches of step i: the trace hook / its callback is due (batched: at the next
+                                        flush that happens; else at once)
+        ('fill', i, g)                  zero-fill of gap g of step i's src_grad
+        ('bn', i, dA, splitk, done)     BatchNorm backward of conv / convT i; dA: 'grad' the gradient buffer, 'pool' the pooled
+                                        gradient as well, 'head' formed from dlogits, 'slabs' the splitk split-K slabs step i + 1
+                                        left; done: step i's hand-over event rides on this launch
+        ('wait', i)  ('order', i)       the hand-over of dz: stream 1 waits for that event / an event recorded behind the launch
+        ('wgrad', i, stream, queued)    weight gradient of conv / convT i; queued: its slab reduce is recorded into the reduce queue
+        ('dgrad', i, slabs)             data gradient of conv / convT i; slabs: it leaves its split-K slabs (accumulate = 2)
+        ('head', i, stream, part)       the head's 'wgrad', 'dgrad', or 'both' as its one combined launch
+        ('op', i)                       step i ('sa', 'pool', 'up') as a whole on the main stream
+        ('flush', i, stream, last)      after step i: flush the reduce queue on `stream` if FLUSH_EVERY reduces are pending (last:
+                                        if any are), then run the callbacks due; queue.pending() is asked when the action runs
+    side: every weight gradient goes to stream 1 as soon as its dz exists, so the HBM-bound kernels of the next layer run in its
+    shadow.  tail_main: the last op of the pass, when it has no data gradient (a stem conv), ends the dependent chain with its
+    BatchNorm backward: its weight gradient runs on that stream beside whatever stream 1 still has queued instead of behind it,
+    its slabs reduced right behind it (handing them to the final batched launch would put two hand-overs and that launch
+    between this kernel and the optimizer: C2 +0.3 %, C4 +0.25 %, C5 +0.15 % same box).  on_kernel: the hand-over event rides on
+    the BatchNorm backward's last dispatch -- no record packet between that launch and the data-gradient convolution on its
+    queue.  batched: the slab reduces run as one launch per FLUSH_EVERY layers (Plan._backward_run)."""
+    acts = [('fork',)] if side else []
+    for i, st in reversed(list(enumerate(steps))):
+        kind, sg = st['kind'], st.get('src_grad')
+        acts.append(('begin', i))
+        acts += [('fill', i, g) for g in range(len(sg['gaps']))] if sg is not None else []
+        if kind == 'head':
+            assert sg is None or not sg['accumulate']
+            # (dgrad_fused: the data gradient is formed by the BatchNorm backward of the layer below; lazy_prod: the activation
+            # under the head was never stored, its weight gradient recomputes it from z)
+            dgrad = sg is not None and not st.get('dgrad_fused')
+            if side and sg is not None:
+                # the head's weight gradient (one pass over the widest feature map) has no consumer until the optimizer:
+                # stream 1, so that the dependent chain starts with the data gradient alone
+                acts += [('head', i, 1, 'wgrad')] + [('head', i, 0, 'dgrad')] * dgrad
+            elif st.get('lazy_prod') is not None or not dgrad:
+                acts += [('head', i, 0, 'wgrad')] + [('head', i, 0, 'dgrad')] * dgrad
+            else:
+                acts.append(('head', i, 0, 'both'))
+        elif kind in ('conv', 'convT'):
+            after = steps[i + 1] if i + 1 < len(steps) else {}
+            away = side and not (tail_main and i == 0 and sg is None)
+            # (fold_dgrad: select_fusions sets it where step i + 1 is the sole reader of this layer's activation -- no head, no pool)
+            dA = 'slabs' if after.get('fold_dgrad') else 'head' if st.get('head_fuse') is not None else \
+                'pool' if st.get('pool_fuse') is not None else 'grad'
+            acts.append(('bn', i, dA, after['plan_d'] >> 8 if dA == 'slabs' else 0, away and on_kernel))
+            if away:
+                acts.append(('wait' if on_kernel else 'order', i))
+            acts.append(('wgrad', i, int(away), batched and kind == 'conv' and (away or not side)))
+            if sg is not None:
+                acts.append(('dgrad', i, bool(st.get('fold_dgrad'))))
+        elif kind == 'sa' or (sg is not None and (kind == 'up' or (kind == 'pool' and not st.get('bwd_fused')))):
+            acts.append(('op', i))               # (bwd_fused: the pooling's backward runs in its producers, pool_fuse)
+        acts.append(('end', i))
+        if batched:
+            acts.append(('flush', i, int(side), i == 0))
+    return acts + [('join',)] * int(side)
+
+
 def _pack_slot(mode, direction):
     """step key of a conv's filter pack of one direction ('f' | 'd'): 'wf' / 'wd' direct kernel, 'uf' / 'ud' the others"""
     return ('u' if mode else 'w') + direction
@@ -556,12 +620,12 @@ class _Cover(object):
 # The keys of a plan's step dicts (plan.steps[i]: the graph op's own keys -- kind, src, dst, conv, bn, mod, lane, lane_split --
 # plus these).  "fusions": decided by select_fusions, written by Plan.__init__ with indices resolved to step dicts and
 # [root, c0, C] to GTensor slices; "conv": select_conv's result as it is; "init" / "bwd": allocated by Plan.__init__ /
-# _prepare_backward.
+# _prepare_backward.  backward (*): backward_schedule decides on it, Plan._backward_launch reads its value.
 #
 #   key                          set by     read by                      meaning
-#   wino_f wino_d wino_w         conv       _forward_op _backward_op     kernel family per direction
-#     plan_f plan_d                         _pack_filters                variant | splitk << 8 of the forward / dgrad launch
-#     wg_target wg_bytes                    _backward_op _prepare_backward   weight gradient: workgroup target, workspace bytes
+#   wino_f wino_d wino_w         conv       _forward_op _backward_launch kernel family per direction
+#     plan_f plan_d                         _pack_filters, executors     variant | splitk << 8 of the forward / dgrad launch
+#     wg_target wg_bytes                    _backward_launch _prepare_backward  weight gradient: workgroup target, workspace bytes
 #     stats_parts fold                      _forward_op _bn_apply        conv-epilogue statistics partials; eval BatchNorm fold
 #     z_bf16 dz_bf16                        __init__ _prepare_backward   storage of z / dz
 #   wf wd uf ud                  init       _pack_filters, executors     filter packs (_pack_slot); flops, pack_key beside them
@@ -574,16 +638,16 @@ class _Cover(object):
 #                                                                        + ReLU; first channel of its rows in the reader's in_tab
 #   in_tab                       init       _forward_op                  that reader's [groups, Cin, 2] (scale, shift) table
 #   head_lazy, head_tab          fusions    _forward_op, tests           the head applies this layer's BatchNorm + ReLU; its table
-#   lazy_prod                    fusions    _forward_op _backward_op     head: the head_lazy step under it
+#   lazy_prod                    fusions    _forward_op, backward (*)    head: the head_lazy step under it
 #   pool_out                     fusions    _bn_apply                    pooled slice this layer's BatchNorm forward also writes
 #   fwd_fused                    fusions    _forward_op _forward_impl, tests   pool: written by its producers (pool_out); training plans only
-#   src_grad                     fusions    _backward_op                 None (network input) | dict(accumulate, gaps to zero-fill)
-#   fold_dgrad                   fusions    _backward_op                 split-K dgrad slabs summed by the BatchNorm backward before
-#   pool_fuse                    fusions    _backward_op                 pooled-gradient slice this layer's BatchNorm backward routes
-#   bwd_fused                    fusions    _backward_op, tests          pool: its backward runs in its producers (pool_fuse)
-#   head_fuse                    fusions    _backward_op, tests          head step whose data gradient this BatchNorm backward forms
-#   dgrad_fused                  fusions    _backward_op                 head: its data gradient is formed below it (head_fuse)
-#   dz wg_off wg_ws ev           bwd        _backward_op                 dz buffer, weight-gradient slab region, hand-over event
+#   src_grad                     fusions    backward (*)                 None (network input) | dict(accumulate, gaps to zero-fill)
+#   fold_dgrad                   fusions    backward_schedule            split-K dgrad slabs summed by the BatchNorm backward before
+#   pool_fuse                    fusions    backward (*)                 pooled-gradient slice this layer's BatchNorm backward routes
+#   bwd_fused                    fusions    backward_schedule, tests     pool: its backward runs in its producers (pool_fuse)
+#   head_fuse                    fusions    backward (*), tests          head step whose data gradient this BatchNorm backward forms
+#   dgrad_fused                  fusions    backward_schedule            head: its data gradient is formed below it (head_fuse)
+#   dz wg_off wg_ws ev           bwd        _backward_run, _launch       dz buffer, weight-gradient slab region, hand-over event
 class Plan(object):
     def __init__(self, graph, params, n, h, w, device, training, precision='fp32', groups=1, shared=None, cfg=None):
         self.g, self.N, self.H, self.W, self.dev, self.training = graph, n, h, w, device, training
@@ -695,7 +759,7 @@ class Plan(object):
                 if st['kind'] == 'pool' and st.get('lane_split'):
                     st['ev_b'] = ops.new_event()
         self._max_wg = max_wg
-        self.wg_ws = self.wg_queue = self._wq_active = None
+        self.wg_ws = self.wg_queue = None
         self._bwd_ready = False
         self.profiler = None             # set by Engine (bench.py's per-kernel HIP-event timing)
         self._pack_key, self._pack_tabs, self._pack_ids, self.side_fwd = None, {}, None, None
@@ -705,6 +769,7 @@ class Plan(object):
         self.side = _side_stream(device) if (training and groups == 1) else None
         self._convs = self._conv_wslots = None
         self.gate_index, self._lane_schedules = gate_step(self.steps), {}    # (dual, free) -> lane_schedule(...): both switch at run time
+        self._backward_schedules = {}    # (side, tail_main, on_kernel, batched) -> backward_schedule(...)
         self._tape_f = self._tape_b = None
         self._coef_key, self._coef_tensors, self._coef_ok, self._coef_next, self._coef_bns = None, None, False, None, []
         self._fp = None
@@ -1089,6 +1154,12 @@ class Plan(object):
             ops.bn_relu_apply(z, a, st['scale'], st['shift'], True)
 
     # ------------------------------------------------------------------ backward
+    def wgrad_stream(self):
+        """the weight-gradient stream of the next backward pass, for the pass itself and for a gradient reducer (Engine.side_stream);
+        None: one stream -- overlap off, or a profiler attached (an event pair then brackets exactly one kernel's own time, not its
+        time under contention with the other stream: bench.py instruments a single step for that reason)"""
+        return self.side if (self.overlap and self.profiler is None) else None
+
     def backward(self, inputs, dlogits, flat, offsets, after_op=None):
         """flat: 1-D fp32 buffer receiving every parameter gradient at offsets[param index]."""
         if self.groups > 1:
@@ -1100,14 +1171,7 @@ class Plan(object):
             i = self.pindex[id(p)]
             return flat[offsets[i]:offsets[i] + p.numel()].view(p.shape)
 
-        # Two streams: the main stream carries the dependent chain (BN backward -> dgrad -> pool /
-        # up-sampling backward); every weight-gradient kernel (MFMA-bound, off the critical path) goes to
-        # a side stream as soon as its dz exists, so the HBM-bound kernels of the next layer run in
-        # its shadow instead of between two MFMA kernels.
-        main = torch.cuda.current_stream()
-        # (with a profiler attached the step runs on ONE stream: an event pair then brackets exactly one kernel's own time,
-        # not its time under contention with the side stream -- bench.py instruments a single step for that reason)
-        side = self.side if (self.overlap and self.profiler is None) else None
+        main, side = torch.cuda.current_stream(), self.wgrad_stream()
         if self._tapeable() and self._fp is not None and self._tape_f is not None:
             # re-issue the recorded launch sequence (aide_amd/tape.py); Python callbacks of a gradient all-reduce hook are
             # tape entries.  Keyed on everything the sequence bakes in.
@@ -1133,179 +1197,120 @@ class Plan(object):
                     tp.py(lambda: after_op(w_st))
                     after_op(w_st)
             with tp:
-                self._backward_streams(inputs, dlogits, gslot, main, side, cb)
+                self._backward_run(inputs, dlogits, gslot, main, side, cb)
             self._tape_b = tp.finish(dyn)
             return
-        self._backward_streams(inputs, dlogits, gslot, main, side, after_op)
+        self._backward_run(inputs, dlogits, gslot, main, side, after_op)
 
-    def _backward_streams(self, inputs, dlogits, gslot, main, side, after_op):
+    def _backward_run(self, inputs, dlogits, gslot, main, side, after_op):
+        """The backward launch sequence: what runs where, and every fork, hand-over, flush point and join, is
+        backward_schedule's; the loop holds no state but the callbacks that wait for a flush.  (The second encoder's chains on a
+        stream of their own, as in the forward pass, measured +-0 beside the weight-gradient stream -- HISTORY §3c: not built in.)"""
         # raw stream handles: every fork / join below is a C-ABI call (ops.order) and every side-stream launch takes the
         # stream explicitly (ops.use_stream) -- nothing here depends on torch's stream context, so the whole sequence can be
         # recorded and re-issued by a launch tape
-        mp = ctypes.c_void_p(main.cuda_stream)
-        sp = ctypes.c_void_p(side.cuda_stream) if side is not None else None
-        if side is not None:
-            ops.order(self.ev_fork, mp, sp)
+        lanes = (ctypes.c_void_p(main.cuda_stream), ctypes.c_void_p(side.cuda_stream) if side is not None else None)
         # The slab reduces of the weight gradients run batched, one launch per FLUSH_EVERY layers: fewer latency-bound
         # launches on the weight-gradient stream, and only the last (small, shallow-encoder) batch sits after the last kernel
         # (bf16 mode: its weight-gradient slabs are several times larger and the batched reduce measured 1 % slower -> per
         # layer).  The queue of pending reduces is this plan's own object (ops.WgradQueue): the library keeps no state.
-        queue = self.wg_queue if (self.profiler is None and self.precision != 'bf16') else None
-        waiting = []                          # ops whose after_op callback waits for the flush of their weight gradient
-
-        def flush():
-            # (pending(): a host-state query decides WHERE the flushes go while recording; a replayed tape re-issues them)
-            if queue.pending():
-                queue.flush(sp if side is not None else mp)
-            if after_op is not None:
-                for w_st in waiting:          # their weight gradients are now enqueued in full
-                    after_op(w_st)
-            del waiting[:]
-
-        hook = after_op
+        batched = self.profiler is None and self.precision != 'bf16'
+        key = (side is not None, self.cfg.tail_wgrad_main and self.profiler is None, self.cfg.handover_on_kernel, batched)
+        if key not in self._backward_schedules:
+            self._backward_schedules[key] = backward_schedule(self.steps, *key)
+        queue = self.wg_queue if batched else None
+        waiting = []                          # steps whose after_op callback waits for the flush of their weight gradient
         if queue is not None:
             queue.discard()                   # (entries of a pass that died between its launches and its flush)
-
-            def hook(w_st):
-                waiting.append(w_st)
-                if queue.pending() >= FLUSH_EVERY:
-                    flush()
-        self._wq_active = queue
         try:
-            with ops.use_stream(mp):
-                self._backward_ops(inputs, dlogits, gslot, mp, sp, hook)
-            if queue is not None:
-                flush()
+            for a in self._backward_schedules[key]:
+                act, st = a[0], self.steps[a[1]] if len(a) > 1 else None
+                if act == 'fork':
+                    ops.order(self.ev_fork, lanes[0], lanes[1])
+                elif act == 'join':
+                    ops.order(self.ev_join, lanes[1], lanes[0])
+                elif act == 'begin':
+                    if self.trace is not None:
+                        self.trace('b', st)
+                elif act == 'end':
+                    if queue is not None:
+                        waiting.append(st)
+                    elif after_op is not None:
+                        after_op(st)
+                elif act == 'wait':
+                    ops.wait(lanes[1], st['ev'])
+                elif act == 'order':
+                    ops.order(st['ev'], lanes[0], lanes[1])
+                elif act == 'flush':
+                    # (pending(): a host-state query decides WHERE the flushes go while recording; a replayed tape re-issues them)
+                    if a[3] or queue.pending() >= FLUSH_EVERY:
+                        if queue.pending():
+                            queue.flush(lanes[a[2]])
+                        for w_st in waiting if after_op is not None else ():     # their weight gradients are now enqueued in full
+                            after_op(w_st)
+                        del waiting[:]
+                else:
+                    with ops.use_stream(lanes[a[2] if act in ('wgrad', 'head') else 0]):
+                        self._backward_launch(a, st, inputs, dlogits, gslot, queue)
         except BaseException:
             if queue is not None:             # the queued descriptors point into this step's arena and workspaces
                 queue.discard()
             raise
-        if side is not None:
-            ops.order(self.ev_join, sp, mp)
 
-    def _backward_ops(self, inputs, dlogits, gslot, main, side, after_op):
-        """The backward launch sequence: the dependent chain on `main`, every weight gradient on `side`.  (The second
-        encoder's chains on a stream of their own, as in the forward pass, measured +-0 beside the weight-gradient stream
-        -- HISTORY §3c -- and is not built in.)"""
-        fold = [0]                       # split count of the data gradient the NEXT BatchNorm backward reads from sk_ws
-        for st in reversed(self.steps):
-            if self.trace is not None:
-                self.trace('b', st)
-            self._backward_op(st, inputs, dlogits, gslot, main, side, self.bn_ws, self.sk_ws, fold)
-            if after_op is not None:
-                after_op(st)
-
-    def _wgrad_handover(self, st, wgrad, tail, done, main, side):
-        """run a layer's weight gradient `wgrad()`: on the weight-gradient stream once its dz exists (`done`: the event of the
-        BatchNorm backward's last dispatch, else one recorded here), or in place (no such stream, or the tail op of the pass)"""
-        if side is None or tail:
-            return wgrad()
-        if done is not None:
-            ops.wait(side, done)
-        else:
-            ops.order(st['ev'], main, side)
-        with ops.use_stream(side):
-            wgrad()
-
-    def _backward_op(self, st, inputs, dlogits, gslot, main, side, bn_ws, sk_ws, folded):
-        """one op of the backward sequence on stream `main` (its lane's stream); folded: [split count] cell of the lane"""
-        kind = st['kind']
-        sg = st.get('src_grad')
-        if sg is not None:
-            for gap in sg['gaps']:
-                ops.fill_zero(self.gview(gap))
-        if kind == 'head':
-            conv = st['conv']
-            k = conv.out_channels
-            assert sg is None or not sg['accumulate']
-            fused = bool(st.get('dgrad_fused'))     # the data gradient is formed by the BatchNorm backward of the layer below
-            dsrc = self.gview(st['src']) if (sg is not None and not fused) else None
-            lp = st.get('lazy_prod')              # the activation under the head was never stored: recomputed from z
-
-            def wgrad_only():
-                if lp is not None:
-                    ops.head1x1_wgrad_bn(dlogits, lp['z'], lp['scale'], lp['shift'], gslot(conv.weight).view(k, -1),
-                                         gslot(conv.bias), ws=self.head_ws)
-                else:
-                    ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), None,
-                                    gslot(conv.weight).view(k, -1), gslot(conv.bias), ws=self.head_ws)
-            if side is not None and sg is not None:
-                # the head's weight gradient (one pass over the widest feature map) has no consumer until the
-                # optimizer: side stream, so that the dependent chain starts with the data gradient alone
-                with ops.use_stream(side):
-                    wgrad_only()
-                if dsrc is not None:        # (lazy_prod: the activation slot was never written; x only feeds dw, None here)
-                    ops.head1x1_bwd(dlogits, lp['z'] if lp is not None else self.view(st['src'], inputs),
-                                    conv.weight.view(k, -1), dsrc, None, None, ws=self.head_ws)
-            elif lp is not None:
-                wgrad_only()
-                if dsrc is not None:
-                    ops.head1x1_bwd(dlogits, lp['z'], conv.weight.view(k, -1), dsrc, None, None, ws=self.head_ws)
-            else:
-                ops.head1x1_bwd(dlogits, self.view(st['src'], inputs), conv.weight.view(k, -1), dsrc,
-                                gslot(conv.weight).view(k, -1), gslot(conv.bias), ws=self.head_ws)
-        elif kind in ('conv', 'convT'):
+    def _backward_launch(self, a, st, inputs, dlogits, gslot, queue):
+        """the launch of one action of backward_schedule ('fill', 'bn', 'wgrad', 'dgrad', 'head', 'op') on the current stream"""
+        act, kind, prof = a[0], st['kind'], self.profiler
+        if act == 'fill':
+            ops.fill_zero(self.gview(st['src_grad']['gaps'][a[2]]))
+        elif act == 'bn':
             conv, bn = st['conv'], st['bn']
-            z = st['z']
-            dz = st['dz']
-            prof = self.profiler
-            # the last op of the pass, when it has no data gradient (a stem conv): the dependent chain ends with its
-            # BatchNorm backward, so its weight gradient runs on that stream beside whatever the weight-gradient
-            # stream still has queued instead of behind it
-            tail = self.cfg.tail_wgrad_main and st is self.steps[0] and sg is None and prof is None
-            # a layer that hands its dz over to the weight-gradient stream right away: the event rides on the
-            # BatchNorm backward's last dispatch (done=) and the other stream only waits for it -- no record packet
-            # between this launch and the data-gradient convolution on this queue
-            done = st['ev'] if (side is not None and not tail and self.cfg.handover_on_kernel) else None
-            if st.get('head_fuse') is not None and not folded[0]:
+            if a[2] == 'slabs':                  # dA is still in the split-K slabs of the conv after this one
+                fn, dA = ops.bn_relu_bwd_slabs, (self.sk_ws, a[3])
+            elif a[2] == 'head':
                 hconv = st['head_fuse']['conv']
-                ops.bn_relu_bwd_head(dlogits, hconv.weight.view(hconv.out_channels, -1), z, dz, st['mean'], st['rstd'], st['scale'],
-                                     st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
-            elif st.get('pool_fuse') is not None and not folded[0]:
+                fn, dA = ops.bn_relu_bwd_head, (dlogits, hconv.weight.view(hconv.out_channels, -1))
+            elif a[2] == 'pool':
                 # (its activation was max-pooled: the pooled gradient joins dA inside this kernel, no pooling backward pass)
-                ops.bn_relu_bwd_pool(self.gview(st['dst']), self.gview(st['pool_fuse']), z, dz, st['mean'], st['rstd'],
-                                     st['scale'], st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws,
-                                     True, done=done)
-            elif folded[0]:                  # dA is still in the split-K slabs of the conv after this one
-                ops.bn_relu_bwd_slabs(sk_ws, folded[0], z, dz, st['mean'], st['rstd'], st['scale'], st['shift'],
-                                      gslot(bn.weight), gslot(bn.bias), gslot(conv.bias), bn_ws, True, done=done)
-                folded[0] = 0
+                fn, dA = ops.bn_relu_bwd_pool, (self.gview(st['dst']), self.gview(st['pool_fuse']))
             else:
-                ops.bn_relu_bwd(self.gview(st['dst']), z, dz, st['mean'], st['rstd'], st['scale'],
-                                st['shift'], gslot(bn.weight), gslot(bn.bias), gslot(conv.bias),
-                                bn_ws, True, done=done)
-            x = self.view(st['src'], inputs)
-            if kind == 'conv':
-                fam_w = FAMILIES[st['wino_w']]
-                # (tail) its slabs are reduced right behind it on this stream (queue = None): handing them to the
-                # final batched launch of the weight-gradient stream would put two stream hand-overs and that
-                # launch between this kernel and the optimizer (C2 +0.3 %, C4 +0.25 %, C5 +0.15 % same box)
-                wq = None if (tail and side is not None) else self._wq_active
-
-                def wgrad():
-                    if prof is not None:
-                        prof.begin(fam_w.wgrad_tag, st['flops'], st['flops'] * fam_w.exec_frac)
-                    fam_w.wgrad(dz, x, gslot(conv.weight), ws=st['wg_ws'], queue=wq, **_wgrad_extra(st))
-                    if prof is not None:
-                        prof.end()
-                self._wgrad_handover(st, wgrad, tail, done, main, side)
-                if sg is not None:
-                    fam_d = FAMILIES[st['wino_d']]
-                    if prof is not None:
-                        prof.begin(fam_d.fwd_tag, st['flops'], st['flops'] * fam_d.exec_frac)
-                    # (fold_dgrad: the split-K slabs stay for the BatchNorm backward before this layer -- Winograd launches only)
-                    assert not st['fold_dgrad'] or fam_d.mode in (2, 4)
-                    fam_d.conv(dz, st[_pack_slot(fam_d.mode, 'd')], None, self.gview(st['src']),
-                               accumulate=2 if st['fold_dgrad'] else sg['accumulate'], plan=st['plan_d'], ws=sk_ws)
-                    if prof is not None:
-                        prof.end()
-                    if st['fold_dgrad']:
-                        folded[0] = st['plan_d'] >> 8
+                fn, dA = ops.bn_relu_bwd, (self.gview(st['dst']),)
+            fn(*(dA + (st['z'], st['dz'], st['mean'], st['rstd'], st['scale'], st['shift'], gslot(bn.weight), gslot(bn.bias),
+                       gslot(conv.bias), self.bn_ws, True)), done=st['ev'] if a[4] else None)
+        elif act == 'wgrad':
+            x, dw = self.view(st['src'], inputs), gslot(st['conv'].weight)
+            if kind == 'convT':
+                ops.convT2x2_wgrad(x, st['dz'], dw, ws=st['wg_ws'])
             else:
-                self._wgrad_handover(st, lambda: ops.convT2x2_wgrad(x, dz, gslot(conv.weight), ws=st['wg_ws']), tail, done,
-                                     main, side)
-                if sg is not None:
-                    ops.convT2x2_dgrad(dz, conv.weight, self.gview(st['src']))
+                fam = FAMILIES[st['wino_w']]
+                if prof is not None:
+                    prof.begin(fam.wgrad_tag, st['flops'], st['flops'] * fam.exec_frac)
+                fam.wgrad(st['dz'], x, dw, ws=st['wg_ws'], queue=queue if a[3] else None, **_wgrad_extra(st))
+                if prof is not None:
+                    prof.end()
+        elif act == 'dgrad':
+            if kind == 'convT':
+                ops.convT2x2_dgrad(st['dz'], st['conv'].weight, self.gview(st['src']))
+            else:
+                fam = FAMILIES[st['wino_d']]
+                if prof is not None:
+                    prof.begin(fam.fwd_tag, st['flops'], st['flops'] * fam.exec_frac)
+                # (slabs: the split-K slabs stay for the BatchNorm backward before this layer -- Winograd launches only)
+                assert not a[2] or fam.mode in (2, 4)
+                fam.conv(st['dz'], st[_pack_slot(fam.mode, 'd')], None, self.gview(st['src']),
+                         accumulate=2 if a[2] else st['src_grad']['accumulate'], plan=st['plan_d'], ws=self.sk_ws)
+                if prof is not None:
+                    prof.end()
+        elif act == 'head':
+            conv, lp = st['conv'], st.get('lazy_prod')
+            k = conv.out_channels
+            dw, db = gslot(conv.weight).view(k, -1), gslot(conv.bias)
+            if a[3] == 'wgrad' and lp is not None:
+                ops.head1x1_wgrad_bn(dlogits, lp['z'], lp['scale'], lp['shift'], dw, db, ws=self.head_ws)
+            else:
+                # (lazy_prod: the activation slot was never written; the data gradient alone does not read x, z stands in)
+                ops.head1x1_bwd(dlogits, lp['z'] if lp is not None else self.view(st['src'], inputs), conv.weight.view(k, -1),
+                                None if a[3] == 'wgrad' else self.gview(st['src']),
+                                *((None, None) if a[3] == 'dgrad' else (dw, db)), ws=self.head_ws)
         elif kind == 'sa':
             m = st['mod']
             y, dout = self.view(st['src'], inputs), self.gview(st['dst'])
@@ -1325,15 +1330,12 @@ class Plan(object):
             ops.pwconv_wgrad(da, y, gslot(m.conv1.weight), gslot(m.conv1.bias))
             # d y = gate * dout (the multiply) + conv1^T d t1, in one pass over the C channels
             ops.pwconv_dgrad(da, m.conv1.weight, self.gview(st['src']), gate=st['gate'], dout=dout,
-                             accumulate=sg['accumulate'])
+                             accumulate=st['src_grad']['accumulate'])
         elif kind == 'pool':
-            if sg is not None and not st.get('bwd_fused'):
-                ops.maxpool2x2_bwd(self.view(st['src'], inputs), self.gview(st['dst']),
-                                   self.gview(st['src']), accumulate=sg['accumulate'])
+            ops.maxpool2x2_bwd(self.view(st['src'], inputs), self.gview(st['dst']), self.gview(st['src']),
+                               accumulate=st['src_grad']['accumulate'])
         elif kind == 'up':
-            if sg is not None:
-                ops.upsample2x_bwd(self.gview(st['dst']), self.gview(st['src']),
-                                   accumulate=sg['accumulate'])
+            ops.upsample2x_bwd(self.gview(st['dst']), self.gview(st['src']), accumulate=st['src_grad']['accumulate'])
 
 
 def _has_param_hooks(params):
@@ -1443,10 +1445,7 @@ class _NetFunction(torch.autograd.Function):
                 else:                    # second backward before the optimizer): one add over the whole arena
                     mode = 3
         flat = arena if mode == 1 else torch.empty(eng.flat_numel, device=dlogits.device, dtype=torch.float32)
-        eng.side_stream = plan.side if (plan._bwd_ready and plan.overlap) else None
-        if not plan._bwd_ready:
-            plan._prepare_backward()
-            eng.side_stream = plan.side if plan.overlap else None
+        eng.side_stream = plan.wgrad_stream()
         if eng.before_backward is not None:
             eng.before_backward(flat)
         plan.backward(ctx.inputs, dlogits, flat, eng.offsets, eng.after_backward_op)

@@ -2,7 +2,10 @@
 -- where the conv-epilogue statistics and with them the lazy BatchNorm paths fire -- against g29 (tools/gen_golden_launch_trace.py,
 recorded on the commit each fixture names): entry-point names, their order and every scalar argument of the forward and backward
 launch tapes, and the (n, total_blocks) of every kernel family's filter-pack tables.  Equality, no tolerance: host-side
-refactors of the engine must not move a launch."""
+refactors of the engine must not move a launch.
+
+The stream every backward launch, hand-over, flush and join goes to, and where the per-step callbacks run, against g31
+(tools/gen_golden_backward_schedule.py): the 64x64 plans regenerated, flush entries included."""
 import json
 import os
 import sys
@@ -45,3 +48,21 @@ def test_launch_trace_matches_fixture(dev, fixture, name):
             for i, (g, w) in enumerate(zip(got[k], want[k])):
                 assert g == w, '%s %s, launch %d: %r, fixture %r' % (name, k, i, g, w)
             assert len(got[k]) == len(want[k])
+
+
+@pytest.mark.gpu
+def test_backward_streams_match_fixture(dev):
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    try:
+        import gen_golden_backward_schedule as G
+    finally:
+        sys.path.pop(0)
+    with open(G.OUT) as f:
+        want = G.unpack(json.load(f))
+    small = [p for p in want if p['spec']['h'] == 64]
+    assert len(small) == 8 and [p['spec'] for p in want] == G.PLANS
+    for p in small:
+        got = json.loads(json.dumps(G.read_plan(p['spec'], dev)))
+        assert got['nsteps'] == p['nsteps'] and len(got['log']) == len(p['log']) > 100, p['spec']
+        for i, (g, w) in enumerate(zip(got['log'], p['log'])):
+            assert g == w, '%s, entry %d: %r, fixture %r' % (p['spec'], i, g, w)
