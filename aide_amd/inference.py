@@ -18,6 +18,8 @@ from ._lib import lib, check
 from .ops import ptr, stream_ptr
 from .ensemble import (VIEW_SETS, view_codes, view_apply_host, view_invert_host, view_stack, ensemble_vote,  # noqa: F401
                        ensemble_vote_host, ensemble_logits, predict_ensemble)
+from .window import (window_grid, window_weights, window_stack, window_blend, window_blend_host,  # noqa: F401
+                     predict_windows)
 
 
 def label_map(logits):
@@ -40,11 +42,19 @@ def predict_labels(net, *modal_inputs, **kw):
     predicted under each of the V views and the label is the first class of the largest mean soft-max (`ensemble_vote`);
     `net` may then be a list / tuple of networks of one class count that vote together (member i * V + j = network i under
     view j, at most 16 members, ValueError beyond), and a forward batch is V views of max(1, batch_size // V) slices.
-    views=None (the default) with one network: the single identity forward and `label_map`, as before."""
+    views=None (the default) with one network: the single identity forward and `label_map`, as before.
+    window=wh or (wh, ww) (multiples of 16, the training size): sliding-window inference for slices of any H x W
+    (aide_amd/window.py) -- windows at stride= (default: half the window), each forwarded (under every view, when views are
+    given), their soft-max maps blended with window_weights= 'gaussian' (sigma_scale=0.125) or 'uniform'; the label is the first
+    class of the largest blended probability, on the native grid.  stride / window_weights / sigma_scale without window:
+    TypeError.  window=None (the default): every call takes the path it took before."""
     batch_size = kw.pop('batch_size', 16)
     views = kw.pop('views', None)
+    win = _window_kw(kw)
     if kw:
         raise TypeError('unexpected arguments %r' % sorted(kw))
+    if win is not None:
+        return predict_windows(net, modal_inputs, views=views, batch_size=batch_size, **win)
     if views is not None or isinstance(net, (list, tuple)):
         return predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size)
     if net.training:
@@ -60,6 +70,18 @@ def predict_labels(net, *modal_inputs, **kw):
     return torch.cat(out, 0) if len(out) > 1 else out[0]
 
 
+def _window_kw(kw):
+    """pops window / stride / window_weights / sigma_scale -> the keywords of `predict_windows`, or None without a window"""
+    given = sorted(k for k in ('stride', 'window_weights', 'sigma_scale') if k in kw)
+    window = kw.pop('window', None)
+    if window is None:
+        if given:
+            raise TypeError('%s go with window=' % ' / '.join(given))
+        return None
+    return dict(window=window, stride=kw.pop('stride', None), weights=kw.pop('window_weights', 'gaussian'),
+                sigma_scale=kw.pop('sigma_scale', 0.125))
+
+
 _UNSET = object()
 
 
@@ -71,6 +93,8 @@ def predict_case(net, *modal_inputs, **kw):
     numpy=False: the [H,W,S] HIP tensor instead (a permuted view of the [S,H,W] labels when unfiltered).
     views=...: the voted labels of `predict_labels(..., views=...)` (`net` may be a list of networks); probs=True then returns
     (volume, mean probabilities [S,C,H,W]) -- the probabilities are the vote's, before any filter.
+    window= / stride= / window_weights= / sigma_scale=: the sliding-window labels of `predict_labels(..., window=...)`; with
+    probs=True the probabilities are the blended ones [S,C,H,W]; the filters and fill_holes run on the blended labels.
     top_k= / min_voxels=: the filter `keep_largest` selects becomes `keep_components` with them (True: one slot; 'per_class':
     one per class, sequences allowed); TypeError when keep_largest is False.  fill_holes=True: `fill_holes` after the filter, on
     its uint8 output, binary or per class as the filter is (keep_largest=False: binary unless num_classes is given), along
@@ -104,9 +128,13 @@ def predict_case(net, *modal_inputs, **kw):
     if want_probs:
         views = kw.pop('views', None)
         batch_size = kw.pop('batch_size', 16)
+        win = _window_kw(kw)
         if kw:
             raise TypeError('unexpected arguments %r' % sorted(kw))
-        vol, pr = predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size, probs=True)
+        if win is not None:
+            vol, pr = predict_windows(net, modal_inputs, views=views, batch_size=batch_size, probs=True, **win)
+        else:
+            vol, pr = predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size, probs=True)
         vol = vol.permute(1, 2, 0)
     else:
         vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)

@@ -773,6 +773,32 @@ int aide_ensemble_vote(const float* const* logits /* HOST array of K device poin
                        long long* labels /* [N][H][W] */, float* probs /* NULL or [N][C][H][W] */, int64_t p_bs,
                        aide_stream_t stream);
 
+/* ---- sliding-window inference (csrc/window.hip): overlapping windows of an image and the weighted blend of their soft-max
+ * maps, for images that are not the training size.  Along an axis of length `size` the windows of length `win` start at the
+ * HOST array starts[count], 1 <= count <= 32: starts[0] = 0, strictly increasing, every start in [0, max(0, size - win)], no
+ * two neighbours more than `win` apart and, when size > win, the last start = size - win -- so every pixel is covered
+ * (aide_amd/window.py `window_grid` makes such tables).  Window b = a_y * nx + a_x, B = ny * nx.  Both calls return
+ * AIDE_ERR_ARG before any launch for a null pointer, a table that breaks one of these rules, a non-positive extent, or 2^31
+ * or more elements in an operand (N * C * H * W, B * N * C * wh * ww).  One launch each, no atomics, no workspace: the same
+ * bytes from call to call. */
+/* y[B][N][C][wh][ww] (image stride y_bs floats, image b * N + n): y[b][n][c][u][v] = x[n][c][min(sy_b + u, H - 1)][min(sx_b + v,
+ * W - 1)], x[N][C][H][W] (image stride x_bs); any C >= 1.  Replaces B slices `x[:, :, sy:sy + wh, sx:sx + ww]` and their
+ * torch.stack (plus F.pad(mode='replicate') where the image is smaller than the window). */
+int aide_window_stack(const float* x, int64_t x_bs, float* y, int64_t y_bs, int N, int C, int H, int W, int wh, int ww,
+                      const int* starts_y /* HOST [ny] */, int ny, const int* starts_x /* HOST [nx] */, int nx,
+                      aide_stream_t stream);
+/* The weighted blend (C = 2 .. aide_seg_max_classes()): for output pixel (n, i, j) and the windows b that contain it, in
+ * increasing b, with (u, v) = (i - sy_b, j - sx_b): p = the C values of src[b][n][.][u][v] (src_is_logits = 0) or their fp32
+ * soft-max as aide_ensemble_vote takes it (src_is_logits != 0); w = g_h[u] * g_w[v]; acc_c = acc_c + w * p_c; den = den + w,
+ * every product and sum rounded to fp32 on its own.  labels[N][H][W] = the FIRST index of the largest acc_c; probs (NULL, or
+ * [N][C][H][W] with image stride p_bs) = acc_c / den.  Window pixels beyond the image are never read.  Replaces per window
+ * F.softmax, a weighted `index_add_` / slice accumulation into [N][C][H][W], the division and torch.argmax. */
+int aide_window_blend(const float* src /* [B][N][C][wh][ww], image stride src_bs */, int src_is_logits, int64_t src_bs,
+                      int N, int C, int H, int W, int wh, int ww, const int* starts_y /* HOST [ny] */, int ny,
+                      const int* starts_x /* HOST [nx] */, int nx, const float* g_h /* DEVICE [wh] */,
+                      const float* g_w /* DEVICE [ww] */, long long* labels /* [N][H][W] */,
+                      float* probs /* NULL or [N][C][H][W] */, int64_t p_bs, aide_stream_t stream);
+
 /* ---- loader transforms of the proposed loaders: Resize(BILINEAR) -> RandomRotate(BILINEAR) -> RandomHorizontallyFlip
  * -> ToTensor -> Normalize (datasetchaos_proposed/transform.py; the single-modal copies of datasetkidney_proposed/ etc.), and
  * Resize(NEAREST) + one_hot_mask of the masks (datasetchaos_proposed/dataset.py).  Bit-exact with PIL where PIL is integer.
