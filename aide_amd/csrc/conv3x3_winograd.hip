@@ -13,14 +13,27 @@
 //     32 co x 32 tiles x 16 positions = 16 accumulators (256 registers, one wave per SIMD);
 //   * filters arrive pre-transformed (aide_conv3x3_wino_pack_multi: U[ci/8][16][co][8 ci]); the input transform runs
 //     inside the kernel: raw halo tile -> LDS, each lane turns one (ci, tile) 4x4 patch into 16 values
-//     (32 adds) and scatters them to V[p][ci][tile]; the output transform (24 adds per 2x2) is
+//     (32 adds) and scatters them to V[p][tile][ci]; the output transform (24 adds per 2x2) is
 //     per-lane on the accumulators, no cross-lane traffic;
-//   * everything is double buffered in LDS and issued in the shadow of the MFMAs (one MFMA per slot).
+//   * raw tile, V and the filters U[p][co][ci] are double buffered in LDS and issued in the shadow of the MFMAs (one MFMA
+//     per slot).  The layouts are NOT conflict-free: the dword patch reads are 2-way (see RCS below), and so are the 16-byte
+//     fragment reads of U and V (a lane's fragment starts 32 bytes after its neighbour's: the 16 lanes of a read group span
+//     512 bytes = two bank rows).  Layouts without these conflicts, and filter fragments loaded global -> registers, were
+//     built and measured: 1-4 % and a further 0-5 % off the kernel alone, nothing in the training step
+//     (profiles/wino2_paths.md), so they are not here;
+//   * the fixed part of a workgroup follows conv3x3_wino4.hip: accumulators zeroed by fenced instructions in the shadow of
+//     the prologue's loads, bias and old outputs as batched buffer loads, outputs through one buffer descriptor per wave
+//     whose range check is the only guard.
 // fp32 F(2x2,3x3) has a forward error of a few ulp (|B|,|A| entries are 0/+-1, G has 1/2): the parity
 // tests hold it to the same 2e-5 as the direct kernels.
 #include "common.h"
 
 namespace {
+
+// buffer store with a 32-bit per-lane byte offset + scalar offset (the loads: common.h); voff = BUF_OOB drops the lane's store
+__device__ __forceinline__ void buf_store_f32x2(f32x2 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
+}
 
 struct WinoArgs {
     const float* x;
@@ -35,7 +48,8 @@ struct WinoArgs {
 constexpr int WCK = 8;                    // input channels per stage
 constexpr int WTCO = 64;                  // output channels per workgroup
 constexpr int RROWS = 18, RRS = 24;       // raw halo tile: 18 rows, row = [3 pad][-1][0..15][16][3 pad]
-constexpr int RCS = RROWS * RRS + 8;      // raw channel stride 440 (= 24 mod 32: conflict-free patch reads)
+constexpr int RCS = RROWS * RRS + 8;      // raw channel stride 440 = 24 (mod 32): the 32 lanes (8 ci x 4 tj) of a half-wave read
+                                          // banks 24 ci + 2 tj -- 16 distinct ones, ci and ci + 4 collide: 2-way
 constexpr int RAWL = WCK * RCS;           // 3520 floats
 constexpr int VL = 16 * 64 * WCK;         // V[p][tile][ci]   (ci minor: one ds_read_b128 = 4 k-steps)
 constexpr int UL = 16 * WTCO * WCK;       // U[p][co][ci]
@@ -43,7 +57,8 @@ constexpr int WBUF = RAWL + VL + UL;      // one stage set (19904 floats = 79.6 
 
 __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];       // 2 * WBUF floats
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave-uniform (scalar) roles
     const int half = lane >> 5, j = lane & 31;
     const int wave_m = wid >> 1, wave_n = wid & 1;
 
@@ -123,7 +138,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) 
     //   xf_store(o) : V[o] <- to[o] for both items                      (2 LDS stores, no VALU)
     // item e of this thread: input channel ci = lane & 7, tile (ti, tj) = (2 wid + e, lane >> 3): a wave
     // writes 64 consecutive floats of V[p][tile][ci] per position (conflict-free) and reads raw patches
-    // at channel stride 440 (conflict-free)
+    // at channel stride 440 (2-way: see RCS)
     f32x2 td[16], to[16];
     const int xci = lane & 7, xtj = lane >> 3;
     const int xr_off = xci * RCS + 4 * wid * RRS + 3 + 2 * xtj;           // item 0; item 1 is 2 rows down
@@ -151,10 +166,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) 
     };
 
     f32x16 acc[16];
-#pragma unroll
-    for (int p = 0; p < 16; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][r] = 0.0f;
 
     float* set0 = lds;
     float* set1 = lds + WBUF;
@@ -163,6 +174,20 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) 
     for (int l = 0; l < NRB + NRC; ++l) fetch_raw(l, c_begin);
 #pragma unroll
     for (int v = 0; v < NU; ++v) fetch_u(v, c_begin);
+    // The accumulators are zeroed HERE, in the shadow of the 13 loads just issued (nothing below can start before they
+    // arrive).  Spelled as instructions and fenced, as in conv3x3_wino4.hip: plain assignments are free to sink behind the
+    // prologue's last vector-memory wait, in front of the barrier that opens the main loop.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float z;
+            asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z));
+            acc[p][r] = z;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int l = 0; l < NRB + NRC; ++l) put_raw(l, set0);
 #pragma unroll
@@ -235,35 +260,60 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) 
     }
 
     // ---- output transform A^T M A per lane, + bias, store 2x2 pixels ----
-    float* yn = a.y + (long)split * a.split_stride + (long)n * a.y_bs;
+    // Lane-derived values are retaken HERE from the lane id (v_mbcnt: two VALU) instead of being carried across the main loop.
+    const int el = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int eh = el >> 5, ej = el & 31;
+    // Outputs, old outputs and bias go through buffer descriptors built once per wave: a 32-bit per-lane offset plus a scalar
+    // row offset instead of a 64-bit address per access, and every guard is a range check -- a lane whose 2x2 block lies
+    // outside the plane carries BUF_OOB (stores dropped, loads read 0), "no bias" is a descriptor of zero length.  No
+    // exec-masked branch and no select around a memory instruction.  (ez = 0, opaque to hipcc: the descriptors are built
+    // here, behind the main loop, not ahead of it where their SGPRs would be live across it.)
+    int ez;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(ez));
+    const int cw = co0 + wave_m * 32 + ez;                 // first co of this wave (scalar); Cout % 64 == 0: always < Cout
     const bool add_bias = (a.bias != nullptr) && (split == 0);
-    const int tile = wave_n * 32 + j, ti = tile >> 3, tj = tile & 7;
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
+        a.y + (long)split * a.split_stride + (long)n * a.y_bs + ez, 0, (int)BUF_OOB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.bias) + ez, 0, add_bias ? a.Cout * 4 : 0, 0x00020000);
+    const int tile = wave_n * 32 + ej, ti = tile >> 3, tj = tile & 7;
     const int oh = h0 + 2 * ti, ow = w0 + 2 * tj;
     const bool pok = oh < a.H && ow < a.W;                 // H, W are even: the 2x2 block is in or out
-    // bias values and (accumulate form) the old outputs are fetched as ONE batch before the first store: next to their use
-    // each was a dependent global_load -> s_waitcnt vmcnt(0) that also waited for the stores issued before it (stores count
-    // in vmcnt on gfx9) -- one memory round trip per output row
+    // byte offset of this lane's 2x2 block in row (r & 3) + 8 (r >> 2) of the wave's co block (host: planes < 2 GiB)
+    const unsigned yoff = pok ? (unsigned)(4 * eh * HW + oh * a.W + ow) * 4u : BUF_OOB;
+    const unsigned boff = (unsigned)eh * 16u;              // bias: co = cw + (r & 3) + 8 (r >> 2) + 4 half
+    // (scalar row offsets, pinned: left to hipcc the products share a vector register with the lane offset above and every
+    // access becomes a readfirstlane loop)
+    const unsigned wrow = (unsigned)__builtin_amdgcn_readfirstlane(a.W * 4);
+    const unsigned hw4 = (unsigned)__builtin_amdgcn_readfirstlane(HW * 4);
+    const unsigned srow0 = (unsigned)__builtin_amdgcn_readfirstlane(cw * HW * 4);
+    // the 16 bias values and (accumulate form) the 32 old output pairs are ONE batch of buffer loads ahead of the first
+    // store, waited for once: next to their use each was a dependent load -> s_waitcnt vmcnt(0) that also waited for the
+    // stores issued before it (stores count in vmcnt on gfx9)
     float bvs[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wave_m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        bvs[r] = (add_bias && pok && co < a.Cout) ? a.bias[co] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r) bvs[r] = buf_load_f32(brs, boff, (unsigned)(cw + (r & 3) + 8 * (r >> 2)) * 4u);
+    constexpr int RB = 8;                                  // output rows per batch of old-value loads
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int r4 = 0; r4 < 16; r4 += 4) {                   // (old outputs: four accumulator rows per batch -- all 16 spilled)
-        float2 olds[4][2];
+    for (int r0 = 0; r0 < 16; r0 += RB) {
+        f32x2 olds[RB][2];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int co = co0 + wave_m * 32 + q + 8 * (r4 >> 2) + 4 * half;
+        for (int q = 0; q < RB; ++q) olds[q][0] = olds[q][1] = f32x2{0.f, 0.f};
+        if (a.accumulate) {                                // wave-uniform
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-                olds[q][i] = (a.accumulate && pok && co < a.Cout)
-                                 ? *reinterpret_cast<const float2*>(yn + (long)co * HW + (long)(oh + i) * a.W + ow) : make_float2(0.f, 0.f);
+            for (int q = 0; q < RB; ++q) {
+                const int r = r0 + q;
+                const unsigned srow = srow0 + (unsigned)((r & 3) + 8 * (r >> 2)) * hw4;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) olds[q][i] = buf_load_f32x2(yrs, yoff, srow + (unsigned)i * wrow);
+            }
         }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int r = r4 + q;
-            const int co = co0 + wave_m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        for (int q = 0; q < RB; ++q) {
+            const int r = r0 + q;
+            const unsigned srow = srow0 + (unsigned)((r & 3) + 8 * (r >> 2)) * hw4;
             float s[2][4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -271,18 +321,16 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a) 
                 s[0][c] = m0 + m1 + m2;
                 s[1][c] = m1 - m2 - m3;
             }
-            if (pok && co < a.Cout) {
-                const float bv = bvs[r];
+            const float bv = bvs[r];
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    float2 o;
-                    o.x = s[i][0] + s[i][1] + s[i][2] + bv;
-                    o.y = s[i][1] - s[i][2] - s[i][3] + bv;
-                    float2* p = reinterpret_cast<float2*>(yn + (long)co * HW + (long)(oh + i) * a.W + ow);
-                    o.x += olds[q][i].x; o.y += olds[q][i].y;
-                    *p = o;
-                }
+            for (int i = 0; i < 2; ++i) {
+                f32x2 o;
+                o.x = s[i][0] + s[i][1] + s[i][2] + bv;
+                o.y = s[i][1] - s[i][2] - s[i][3] + bv;
+                o.x += olds[q][i].x; o.y += olds[q][i].y;
+                buf_store_f32x2(o, yrs, yoff, srow + (unsigned)i * wrow);
             }
+            __builtin_amdgcn_sched_barrier(0);             // one row at a time
         }
     }
 }
