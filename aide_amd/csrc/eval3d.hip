@@ -43,6 +43,21 @@
 //   holes                  (aide_fill_holes3d) launches 1 - 3 with the connectivity predicate "value == 0" (launches 1 - 2 take
 //                          the predicate as a template parameter), one word per root that records what the blob touches, a
 //                          write that fills where the word is exactly one class
+//   labelled components    (aide_label_components3d) launches 1 - 3, then the rank of every root = the number of roots with a
+//                          lower node index (roots are first voxels, so this is the blob's number in raster order): a prefix
+//                          sum over the root flags in three launches -- per-block root counts, a scan of the block counts by
+//                          ONE workgroup that loops over them (it is the only workgroup of its launch and reads what the
+//                          launch before it wrote: nothing is looked back at, nothing is waited for), a per-block local scan
+//                          plus the block's offset -- and one write: labels[i] = rank(find(i)) + 1, box and coordinate sums
+//                          of the blobs below the cap with atomicMin / atomicMax / 64-bit atomicAdd, gathered per block in a
+//                          table in LDS first.  Seven launches and at most one memset (the props table), whatever the
+//                          volume, the class count and the cap are
+//   lesion counts          (aide_lesion_counts3d) per volume A of (target, pred), B the other one: launches 1 - 3 on A, one
+//                          launch that adds every voxel of A at which B agrees to cover[find(i)], one that reduces the roots
+//                          into the six columns per class.  Both volumes go through the SAME three words per voxel one after
+//                          the other (parent, area, cover).  Ten launches and three memsets (the table, cover twice).  The
+//                          one non-integer operation of the file is its threshold: double(cover) >= overlap * double(area)
+// In all of them no workgroup ever waits for another.
 #include "common.h"
 
 namespace {
@@ -774,6 +789,336 @@ __global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned c
     if (blockIdx.x == 0 && threadIdx.x == 3) out[4 * k] = n;
 }
 
+// ---- labelled components (aide_label_components3d; the single volume) ----
+// After launches 1 - 3 under Equal every non-zero voxel has a root and every root its area.  A root is a MEMBER root when its
+// value is a member (C = 0: any non-zero value; C >= 2: a class 1 .. C - 1): the blobs of other values exist in `parent` and
+// get label 0.  The rank launches work on blocks of SCAN nodes: 256 threads x 4 nodes, node = block * SCAN + k * 256 + thread,
+// so the order inside a block is (k, wave, lane).
+constexpr int SCAN = 1024;
+constexpr int PROPS = 12;                         // value, area, first, min0..2, max0..2 + 1, sum0..2
+
+__device__ __forceinline__ void node_coords(const View& g, int i, int& i0, int& i1, int& i2) {
+    const int plane = g.d1 * g.d2;
+    i0 = i / plane;
+    const int r = i - i0 * plane;
+    i1 = r / g.d2;
+    i2 = r - i1 * g.d2;
+}
+
+__device__ __forceinline__ long long node_value(const View& g, int i) {
+    int i0, i1, i2;
+    node_coords(g, i, i0, i1, i2);
+    return g.v[g.off(i0, i1, i2)];
+}
+
+// 0: node u is no root (or lies past the volume), 1: a member root, -1: the root of a blob of another value
+__device__ __forceinline__ int root_kind(const View& g, const int* __restrict__ parent, unsigned u, unsigned n, int C) {
+    if (u >= n || parent[u] != (int)u) return 0;
+    if (!C) return 1;
+    return class_of(node_value(g, (int)u), C) ? 1 : -1;
+}
+
+// 4 flag: blockcnt[b] = member roots among the block's SCAN nodes
+__global__ __launch_bounds__(256) void lab_flag_kernel(Strided geo, const int* __restrict__ parent, int C,
+                                                       int* __restrict__ blockcnt) {
+    __shared__ int sm[4];
+    const View g = geo.view();
+    const unsigned n = (unsigned)(g.d0 * g.d1 * g.d2);
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN / 256; ++k)
+        c += root_kind(g, parent, blockIdx.x * (unsigned)SCAN + k * 256u + threadIdx.x, n, C) == 1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) blockcnt[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+}
+
+// 5 scan: ONE workgroup turns the nb block counts into exclusive offsets in place, SCAN_T of them per trip with the running
+// total carried in a register, and writes the number of blobs.  (a total is at most the voxel count < 2^31)
+constexpr int SCAN_T = 1024;
+__global__ __launch_bounds__(SCAN_T) void lab_scan_kernel(int* __restrict__ blockcnt, int nb, long long* __restrict__ count) {
+    __shared__ int wsum[SCAN_T / 64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int carry = 0;
+    for (int o = 0; o < nb; o += SCAN_T) {        // uniform trip count
+        const int j = o + (int)threadIdx.x;
+        const int c = j < nb ? blockcnt[j] : 0;
+        int s = c;                                // inclusive scan of the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(s, d);
+            if (lane >= d) s += t;
+        }
+        if (lane == 63) wsum[wid] = s;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SCAN_T / 64; ++w) {
+            const int x = wsum[w];
+            before += w < wid ? x : 0;
+            total += x;
+        }
+        if (j < nb) blockcnt[j] = carry + before + s - c;
+        carry += total;
+        __syncthreads();                          // wsum is written again
+    }
+    if (threadIdx.x == 0) count[0] = carry;
+}
+
+// 6 rank: rank[i] = the block's offset + the member roots of the block in front of i, at every member root; -1 at the root of
+// any other blob (no other node's word is ever read).  Blob j < cap gets its props row from its root's own thread: value, area,
+// first index, and the box and the sums of the first voxel alone -- write adds the other voxels
+__global__ __launch_bounds__(256) void lab_rank_kernel(Strided geo, const int* __restrict__ parent, const int* __restrict__ area,
+                                                       int C, const int* __restrict__ blockoff, int* __restrict__ rank,
+                                                       long long* __restrict__ props, int cap) {
+    __shared__ int tot[SCAN / 256][4];
+    const View g = geo.view();
+    const unsigned n = (unsigned)(g.d0 * g.d1 * g.d2);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int kind[SCAN / 256], pre[SCAN / 256], base[SCAN / 256];
+#pragma unroll
+    for (int k = 0; k < SCAN / 256; ++k) {
+        kind[k] = root_kind(g, parent, blockIdx.x * (unsigned)SCAN + k * 256u + threadIdx.x, n, C);
+        const unsigned long long b = __ballot(kind[k] == 1);
+        pre[k] = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) tot[k][wid] = __popcll(b);
+    }
+    __syncthreads();
+    int run = blockoff[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < SCAN / 256; ++k)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w == wid) base[k] = run;
+            run += tot[k][w];
+        }
+#pragma unroll
+    for (int k = 0; k < SCAN / 256; ++k) {
+        if (kind[k] == 0) continue;
+        const int i = (int)(blockIdx.x * (unsigned)SCAN + k * 256u + threadIdx.x);
+        const int j = kind[k] == 1 ? base[k] + pre[k] : -1;
+        rank[i] = j;
+        if (props && j >= 0 && j < cap) {
+            int i0, i1, i2;
+            node_coords(g, i, i0, i1, i2);
+            long long* row = props + (long)j * PROPS;
+            row[0] = g.v[g.off(i0, i1, i2)]; row[1] = area[i]; row[2] = i;
+            row[3] = i0; row[4] = i1; row[5] = i2;
+            row[6] = i0 + 1; row[7] = i1 + 1; row[8] = i2 + 1;
+            row[9] = i0; row[10] = i1; row[11] = i2;
+        }
+    }
+}
+
+// 7 write: labels[i] = rank(find(i)) + 1 (0: no member), WRITE_K x 256 consecutive nodes per block.  Props: every voxel but
+// the first of a blob below the cap goes into its row, through a table of TBL slots in LDS per block.  Slot j % TBL belongs to
+// the LOWEST blob number j the block holds there: the first pass over the nodes settles that with atomicMin (after a plain
+// read: the word only decreases, so a value already at or below j needs no atomic) and keeps every voxel's blob in LDS.  The
+// second pass, after a barrier: lanes of a wave that share a blob are reduced first (whole waves, as in count), and the leader
+// adds the wave's part to the blob's slot, or straight to the row where another blob owns the slot.  The slots go to the rows
+// at the end: one set of global atomics per (block, blob) for the owners, per (wave, blob) for the others.  Every part is a
+// min, a max or a sum of integers: the same bytes whichever way a part takes
+constexpr int WRITE_K = 16, TBL = 128;
+
+// a part of blob j goes to its row: the six box words are lowered / raised after a plain load -- it may return an older
+// value, which is no tighter than the word is now, so a coordinate inside it needs no atomic -- and the three sums added
+__device__ __forceinline__ void props_commit(unsigned long long* __restrict__ props, int j, int lo0, int lo1, int lo2, int hi0,
+                                             int hi1, int hi2, unsigned long long s0, unsigned long long s1,
+                                             unsigned long long s2) {
+    unsigned long long* row = props + (long)j * PROPS;
+    if ((unsigned long long)lo0 < row[3]) atomicMin(row + 3, (unsigned long long)lo0);
+    if ((unsigned long long)lo1 < row[4]) atomicMin(row + 4, (unsigned long long)lo1);
+    if ((unsigned long long)lo2 < row[5]) atomicMin(row + 5, (unsigned long long)lo2);
+    if ((unsigned long long)hi0 > row[6]) atomicMax(row + 6, (unsigned long long)hi0);
+    if ((unsigned long long)hi1 > row[7]) atomicMax(row + 7, (unsigned long long)hi1);
+    if ((unsigned long long)hi2 > row[8]) atomicMax(row + 8, (unsigned long long)hi2);
+    atomicAdd(row + 9, s0);
+    atomicAdd(row + 10, s1);
+    atomicAdd(row + 11, s2);
+}
+
+__global__ __launch_bounds__(256) void lab_write_kernel(Strided geo, const int* __restrict__ parent, const int* __restrict__ rank,
+                                                        int* __restrict__ labels, unsigned long long* __restrict__ props, int cap) {
+    __shared__ int key[TBL];                      // the blob that owns the slot, INT32_MAX: none
+    __shared__ int box[6][TBL];
+    __shared__ unsigned long long sum[3][TBL];
+    __shared__ int blob[WRITE_K][256];            // the blob a voxel adds to, -1: none
+    const View g = geo.view();
+    const unsigned n = (unsigned)(g.d0 * g.d1 * g.d2);
+    const int lane = threadIdx.x & 63;
+    if (props) {
+        if (threadIdx.x < TBL) {
+            const int e = threadIdx.x;
+            key[e] = INT32_MAX;
+            box[0][e] = box[1][e] = box[2][e] = INT32_MAX;
+            box[3][e] = box[4][e] = box[5][e] = 0;
+            sum[0][e] = sum[1][e] = sum[2][e] = 0ull;
+        }
+        __syncthreads();
+    }
+    for (int k = 0; k < WRITE_K; ++k) {
+        const unsigned u = (blockIdx.x * (unsigned)WRITE_K + k) * 256u + threadIdx.x;
+        const int i = (int)u;
+        int j = -1, r = -1;
+        if (u < n) {
+            const int p = parent[i];
+            if (p >= 0) {
+                r = find_plain(parent, p);
+                j = rank[r];
+            }
+            labels[i] = j + 1;
+        }
+        if (!props) continue;
+        const bool add = j >= 0 && j < cap && r != i;
+        blob[k][threadIdx.x] = add ? j : -1;
+        if (add) {
+            volatile int* owner = &key[j & (TBL - 1)];
+            if (*owner > j) atomicMin(&key[j & (TBL - 1)], j);
+        }
+    }
+    if (!props) return;
+    __syncthreads();
+    for (int k = 0; k < WRITE_K; ++k) {
+        const int j = blob[k][threadIdx.x];
+        const bool add = j >= 0;
+        unsigned long long pending = __ballot(add);
+        if (!pending) continue;
+        int x0 = 0, x1 = 0, x2 = 0;
+        if (add) node_coords(g, (int)((blockIdx.x * (unsigned)WRITE_K + k) * 256u + threadIdx.x), x0, x1, x2);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int jl = __shfl(j, leader);
+            const bool mine = add && j == jl;
+            int lo0 = mine ? x0 : INT32_MAX, lo1 = mine ? x1 : INT32_MAX, lo2 = mine ? x2 : INT32_MAX;
+            int hi0 = mine ? x0 + 1 : 0, hi1 = mine ? x1 + 1 : 0, hi2 = mine ? x2 + 1 : 0;
+            long long s0 = mine ? x0 : 0, s1 = mine ? x1 : 0, s2 = mine ? x2 : 0;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) {
+                lo0 = min(lo0, __shfl_xor(lo0, d)); lo1 = min(lo1, __shfl_xor(lo1, d)); lo2 = min(lo2, __shfl_xor(lo2, d));
+                hi0 = max(hi0, __shfl_xor(hi0, d)); hi1 = max(hi1, __shfl_xor(hi1, d)); hi2 = max(hi2, __shfl_xor(hi2, d));
+                s0 += __shfl_xor(s0, d); s1 += __shfl_xor(s1, d); s2 += __shfl_xor(s2, d);
+            }
+            if (lane == leader) {
+                const int slot = jl & (TBL - 1);
+                if (key[slot] == jl) {
+                    atomicMin(&box[0][slot], lo0); atomicMin(&box[1][slot], lo1); atomicMin(&box[2][slot], lo2);
+                    atomicMax(&box[3][slot], hi0); atomicMax(&box[4][slot], hi1); atomicMax(&box[5][slot], hi2);
+                    atomicAdd(&sum[0][slot], (unsigned long long)s0);
+                    atomicAdd(&sum[1][slot], (unsigned long long)s1);
+                    atomicAdd(&sum[2][slot], (unsigned long long)s2);
+                } else {
+                    props_commit(props, jl, lo0, lo1, lo2, hi0, hi1, hi2, (unsigned long long)s0, (unsigned long long)s1,
+                                 (unsigned long long)s2);
+                }
+            }
+            pending &= ~__ballot(mine);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < TBL && key[threadIdx.x] != INT32_MAX) {
+        const int e = threadIdx.x;
+        props_commit(props, key[e], box[0][e], box[1][e], box[2][e], box[3][e], box[4][e], box[5][e], sum[0][e], sum[1][e],
+                     sum[2][e]);
+    }
+}
+
+// ---- lesion counts (aide_lesion_counts3d; the single volume) ----
+// After launches 1 - 3 on A.  cover: a voxel of A at which B agrees (C = 0: B != 0; C >= 2: A's value is a class and B holds
+// it too) adds 1 to cover[find(i)].  COVER_K x 256 consecutive nodes per block and the table scheme of the labels' write launch:
+// slot r % TBL of a table in LDS belongs to the lowest root r the block holds there (atomicMin in the first pass, which keeps
+// every voxel's root in LDS); in the second pass the lanes of a wave with the same root are counted with one ballot and the
+// leader adds the count to the root's slot, or straight to cover[r] where another root owns the slot; the slots go to cover at
+// the end: one global atomicAdd per (block, root) for the owners, per (wave, root) for the others
+constexpr int COVER_K = 16;
+__global__ __launch_bounds__(256) void les_cover_kernel(Strided geo, Operand B, const int* __restrict__ parent, int C,
+                                                        int* __restrict__ cover) {
+    __shared__ int key[TBL];                      // the root that owns the slot, INT32_MAX: none
+    __shared__ int cnt[TBL];
+    __shared__ int root[COVER_K][256];            // the root a voxel adds to, -1: none
+    const View g = geo.view();
+    const unsigned n = (unsigned)(g.d0 * g.d1 * g.d2);
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < TBL) { key[threadIdx.x] = INT32_MAX; cnt[threadIdx.x] = 0; }
+    __syncthreads();
+    for (int k = 0; k < COVER_K; ++k) {
+        const unsigned u = (blockIdx.x * (unsigned)COVER_K + k) * 256u + threadIdx.x;
+        int r = -1;
+        if (u < n) {
+            const int i = (int)u, p = parent[i];
+            if (p >= 0) {
+                int i0, i1, i2;
+                node_coords(g, i, i0, i1, i2);
+                const long long b = static_cast<const long long*>(B.p)[(long)i0 * B.s0 + (long)i1 * B.s1 + (long)i2 * B.s2];
+                bool agree = b != 0;
+                if (C) {
+                    const long long a = g.v[g.off(i0, i1, i2)];
+                    agree = class_of(a, C) != 0 && b == a;
+                }
+                if (agree) r = find_plain(parent, p);
+            }
+        }
+        root[k][threadIdx.x] = r;
+        if (r >= 0) {
+            volatile int* owner = &key[r & (TBL - 1)];
+            if (*owner > r) atomicMin(&key[r & (TBL - 1)], r);
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < COVER_K; ++k) {
+        const int r = root[k][threadIdx.x];
+        unsigned long long pending = __ballot(r >= 0);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int rl = __shfl(r, leader);
+            const unsigned long long same = __ballot(r == rl);
+            if (lane == leader) {
+                const int slot = rl & (TBL - 1);
+                if (key[slot] == rl) atomicAdd(&cnt[slot], __popcll(same));
+                else atomicAdd(cover + rl, __popcll(same));
+            }
+            pending &= ~same;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < TBL && key[threadIdx.x] != INT32_MAX) atomicAdd(cover + key[threadIdx.x], cnt[threadIdx.x]);
+}
+
+// reduce: the member roots of A into the columns of its side, per class row (C = 0: row 1).  side 0, A = target: blobs ->
+// column 0, blobs that count -> 1, cover -> 4.  side 1, A = pred: blobs -> 2, blobs that count -> 3, the area of the blobs that
+// do not count -> 5.  A blob counts when cover >= 1 and double(cover) >= overlap * double(area).  Roots are rare: LDS atomics
+// per root, then one global atomicAdd per (block, word) that is not zero
+__global__ __launch_bounds__(256) void les_reduce_kernel(Strided geo, const int* __restrict__ parent, const int* __restrict__ area,
+                                                         const int* __restrict__ cover, int C, double overlap, int side,
+                                                         long long* __restrict__ out) {
+    __shared__ unsigned long long acc[MAXC][4];   // blobs, blobs that count, cover, area of the blobs that do not count
+    if (threadIdx.x < MAXC * 4) (&acc[0][0])[threadIdx.x] = 0ull;
+    __syncthreads();
+    const View g = geo.view();
+    geo.select_nodes(g, [&](int i, auto value_off, long) {
+        if (parent[i] != i) return;
+        int c = 1;
+        if (C) {
+            c = class_of(g.v[value_off()], C);
+            if (!c) return;
+        }
+        const int ar = area[i], cv = cover[i];
+        const bool counts = cv >= 1 && (double)cv >= overlap * (double)ar;
+        atomicAdd(&acc[c][0], 1ull);
+        if (counts) atomicAdd(&acc[c][1], 1ull);
+        if (cv) atomicAdd(&acc[c][2], (unsigned long long)cv);
+        if (!counts) atomicAdd(&acc[c][3], (unsigned long long)ar);
+    });
+    __syncthreads();
+    if (threadIdx.x < MAXC * 4) {
+        const int c = threadIdx.x >> 2, k = threadIdx.x & 3;
+        const int col = side == 0 ? (k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 4 : -1) : (k == 0 ? 2 : k == 1 ? 3 : k == 3 ? 5 : -1);
+        const unsigned long long v = acc[c][k];
+        if (v && col >= 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + c * 6 + col), v);
+    }
+}
+
 // ---- host ----
 bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
     if (d0 < 0 || d1 < 0 || d2 < 0) return false;
@@ -925,9 +1270,113 @@ int holes_launch(const Strided& geo, const Grids& gr, int n, int C, int cut, uns
     return aide_launch_status();
 }
 
+// workspace of the two pipelines below: three int words per voxel (parent, area, and rank or cover), then, 16-byte aligned, the
+// two control words launch 1 clears and (labels) one int per block of SCAN nodes
+struct Carved3 {
+    int *parent, *area, *third;
+    unsigned long long* ctrl;
+    int* blockcnt;
+};
+Carved3 carve3(void* ws, int n) {
+    int* parent = static_cast<int*>(ws);
+    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(parent + 3 * (size_t)n) + 15) & ~static_cast<uintptr_t>(15));
+    return Carved3{parent, parent + n, parent + 2 * (size_t)n, ctrl, reinterpret_cast<int*>(ctrl + 2)};
+}
+size_t ws3_bytes(int64_t nvox, bool blocks) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    return (size_t)(3 * nvox) * sizeof(int) + 16 + 2 * sizeof(unsigned long long) +
+           (blocks ? (size_t)((nvox + SCAN - 1) / SCAN) * sizeof(int) : 0);
+}
+
+constexpr int64_t MAX_BLOBS = 1 << 20;
+
+// labelled components: [memset of props,] launches 1 - 3, flag, scan, rank, write
+int label_components_launch(const Strided& geo, const Grids& gr, int n, int C, int* labels, long long* count, long long* props,
+                            int cap, void* ws, hipStream_t stream) {
+    const Carved3 w = carve3(ws, n);
+    const int* cparent = w.parent;
+    const int* carea = w.area;
+    const int* crank = w.third;
+    const int* coff = w.blockcnt;
+    const int nb = (int)(((long)n + SCAN - 1) / SCAN);
+    const dim3 block(256), scan_grid((unsigned)nb);
+    if (props) {
+        hipError_t e = hipMemsetAsync(props, 0, (size_t)cap * PROPS * sizeof(long long), stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, flag 4, rank 4, write 4 + 4 + 4
+    label_launch(geo, Equal{}, gr, 40.0 * n, w.parent, w.area, w.ctrl, stream);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lab_flag_kernel, scan_grid, block, 0, stream, geo, cparent, C, w.blockcnt);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lab_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, w.blockcnt, nb, count);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lab_rank_kernel, scan_grid, block, 0, stream, geo, cparent, carea, C, coff, w.third, props, cap);
+    const dim3 write_grid((unsigned)(((long)n + WRITE_K * 256 - 1) / (WRITE_K * 256)));
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, lab_write_kernel, write_grid, block, 0, stream, geo, cparent, crank, labels,
+                      reinterpret_cast<unsigned long long*>(props), cap);
+    return aide_launch_status();
+}
+
+// lesion counts of one side: memset of cover, launches 1 - 3 on A, cover, reduce
+int lesion_side_launch(const Strided& geo, const Grids& gr, const Operand& other, int n, int C, double overlap, int side,
+                       long long* out, void* ws, hipStream_t stream) {
+    const Carved3 w = carve3(ws, n);
+    const int* cparent = w.parent;
+    const int* carea = w.area;
+    const int* ccover = w.third;
+    const dim3 block(256);
+    hipError_t e = hipMemsetAsync(w.third, 0, (size_t)n * sizeof(int), stream);
+    if (e != hipSuccess) return (int)e;
+    // algorithmic traffic: V 8 + parent / area 4 + 4 (local), count 4, cover 4 + 8 (+ 8 with classes), reduce 4
+    label_launch(geo, Equal{}, gr, (C ? 44.0 : 36.0) * n, w.parent, w.area, w.ctrl, stream);
+    const dim3 cover_grid((unsigned)(((long)n + COVER_K * 256 - 1) / (COVER_K * 256)));
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, les_cover_kernel, cover_grid, block, 0, stream, geo, other, cparent, C, w.third);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 0.0, les_reduce_kernel, gr.select, block, 0, stream, geo, cparent, carea, ccover, C, overlap,
+                      side, out);
+    return aide_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t aide_label_components3d_ws_bytes(int64_t nvox) { return ws3_bytes(nvox, true); }
+
+int aide_label_components3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                            int num_classes, int* labels, long long* count, long long* props, int64_t max_blobs, void* ws,
+                            hipStream_t stream) {
+    if ((num_classes != 0 && !classes_ok(num_classes)) || !dims_ok(d0, d1, d2) || !count) return AIDE_ERR_ARG;
+    if (props && (max_blobs < 1 || max_blobs > MAX_BLOBS)) return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(count, 0, sizeof(long long), stream);
+        if (e == hipSuccess && props) e = hipMemsetAsync(props, 0, (size_t)max_blobs * PROPS * sizeof(long long), stream);
+        return (int)e;
+    }
+    if (!v || !labels || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
+    Grids gr;
+    const Strided geo = make_strided(v, d0, d1, d2, s0, s1, s2, gr);
+    return label_components_launch(geo, gr, n, num_classes, labels, count, props, props ? (int)max_blobs : 0, ws, stream);
+}
+
+size_t aide_lesion_counts3d_ws_bytes(int64_t nvox) { return ws3_bytes(nvox, false); }
+
+int aide_lesion_counts3d(const long long* pred, int64_t p_s0, int64_t p_s1, int64_t p_s2, const long long* target, int64_t t_s0,
+                         int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, int num_classes, double overlap,
+                         long long* out, void* ws, hipStream_t stream) {
+    if ((num_classes != 0 && !classes_ok(num_classes)) || !dims_ok(d0, d1, d2) || !out) return AIDE_ERR_ARG;
+    if (!(overlap >= 0.0 && overlap <= 1.0)) return AIDE_ERR_ARG;   // (also a NaN)
+    const int n = (int)(d0 * d1 * d2);
+    if (n > 0 && (!pred || !target || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0)) return AIDE_ERR_ARG;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)(6 * (num_classes ? num_classes : 2)) * sizeof(long long), stream);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return 0;
+    Grids gr;
+    const Strided tgeo = make_strided(target, d0, d1, d2, t_s0, t_s1, t_s2, gr);
+    const Operand P{pred, (long)p_s0, (long)p_s1, (long)p_s2}, T{target, (long)t_s0, (long)t_s1, (long)t_s2};
+    if (int rc = lesion_side_launch(tgeo, gr, P, n, num_classes, overlap, 0, out, ws, stream)) return rc;
+    const Strided pgeo = make_strided(pred, d0, d1, d2, p_s0, p_s1, p_s2, gr);
+    return lesion_side_launch(pgeo, gr, T, n, num_classes, overlap, 1, out, ws, stream);
+}
 
 size_t aide_components3d_ws_bytes(int64_t nvox) { return ws_bytes(nvox, 1, KC_WORDS); }
 

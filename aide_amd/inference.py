@@ -563,7 +563,7 @@ def _case_scores_classes(pred, target, c):
     return dict(Dice=dice, IoU=iou, TP=tp.copy(), TN=n - si - st + tp, FP=si - tp, FN=st - tp)
 
 
-def case_scores(pred, target, num_classes=None, spacing=None, percentiles=None, tolerances=None):
+def case_scores(pred, target, num_classes=None, spacing=None, percentiles=None, tolerances=None, lesions=None):
     """Per-case scores of the evaluation script (evalchaos_comparison_1cases.py:116-141, 238-242) for a predicted label
     volume against its target: dict(Dice, IoU, TP, TN, FP, FN).  HIP tensors: one confusion launch and one copy of four
     int64 sums to the host; anything else: the same sums in int64 on the CPU.  TP = sum p*t, FP = sum p - TP,
@@ -576,7 +576,15 @@ def case_scores(pred, target, num_classes=None, spacing=None, percentiles=None, 
     `voxelspacing`, :181, 192-194): the dict also carries RAVD, ASSD and MSSD of `utils.metrics3d.surface_scores`; without it
     the dict is the six scores above and nothing else.
     percentiles=(q, ...) / tolerances=(tau, ...) (1 .. 4 numbers each; they need `spacing`, TypeError without it) go to
-    `surface_scores` and add HD and HD_pooled ([Q], or [C, Q]) / NSD ([T], or [C, T]): percentiles=(95,) is HD95."""
+    `surface_scores` and add HD and HD_pooled ([Q], or [C, Q]) / NSD ([T], or [C, T]): percentiles=(95,) is HD95.
+    lesions=overlap (a number in [0, 1]; 3-D volumes): the dict also carries the nine entries of `lesion_scores(pred, target,
+    num_classes, overlap)`, each key prefixed `lesion_`.  With lesions=None every call takes the path it took without the
+    argument and the dict has the keys it had."""
+    if lesions is not None:
+        overlap = _overlap(lesions, 'case_scores')
+        res = case_scores(pred, target, num_classes, spacing, percentiles, tolerances)
+        res.update(('lesion_' + k, v) for k, v in lesion_scores(pred, target, num_classes, overlap).items())
+        return res
     if spacing is None and (percentiles is not None or tolerances is not None):
         raise TypeError('case_scores: percentiles / tolerances are surface distances and need spacing=(sp0, sp1, sp2)')
     if spacing is not None:
@@ -598,6 +606,206 @@ def case_scores(pred, target, num_classes=None, spacing=None, percentiles=None, 
         dice = np.float64(2 * spt) / np.float64(sp + st)
         iou = np.float64(spt) / np.float64(sp + st - spt)
     return dict(Dice=dice, IoU=iou, TP=spt, TN=n - sp - st + spt, FP=sp - spt, FN=st - spt)
+
+
+# ---- labelled components and lesion-wise detection scores ---------------------------------------------------------------
+MAX_BLOBS = 2 ** 20
+PROPS_COLUMNS = ('value', 'area', 'first', 'min0', 'min1', 'min2', 'max0', 'max1', 'max2', 'sum0', 'sum1', 'sum2')
+LESION_COLUMNS = ('target_blobs', 'detected', 'pred_blobs', 'matched', 'covered_voxels', 'spurious_voxels')
+
+
+def _max_blobs(m):
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= MAX_BLOBS:
+        raise ValueError('label_components: max_blobs %r, an integer in 1 .. 2^20 is expected' % (m,))
+    return int(m)
+
+
+def _overlap(x, what='lesion_scores'):
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not 0.0 <= float(x) <= 1.0:
+        raise ValueError('%s: overlap %r, a number in [0, 1] is expected' % (what, x))
+    return float(x)
+
+
+def _host_volume(x, what):
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise RuntimeError('%s: a 3-D volume is expected, got %d dims' % (what, x.ndim))
+    if x.dtype != np.bool_ and not np.issubdtype(x.dtype, np.integer):
+        raise RuntimeError('%s: integer labels expected, got %s' % (what, x.dtype))
+    return x
+
+
+def _label_host(vol, c):
+    """-> (labels int32, value[n], area[n], first[n]): scipy.ndimage.label once per member value, the blobs of all values
+    then ordered by their first voxel, computed explicitly"""
+    labels = np.zeros(vol.shape, np.int32)
+    empty = np.zeros(0, np.int64)
+    if vol.size == 0:
+        return labels, empty, empty, empty
+    values = range(1, c) if c else [v for v in np.unique(vol).tolist() if v != 0]
+    found = [(v,) + _blobs_of(vol, v) for v in values]
+    value = np.concatenate([np.full(len(a), v, np.int64) for v, _, a, _ in found] + [empty])
+    area = np.concatenate([a for _, _, a, _ in found] + [empty]).astype(np.int64)
+    first = np.concatenate([f for _, _, _, f in found] + [empty]).astype(np.int64)
+    order = np.argsort(first, kind='stable')      # (first voxels are distinct)
+    number = np.empty(len(order), np.int64)
+    number[order] = np.arange(1, len(order) + 1)
+    at = 0
+    for _, blobs, a, _ in found:
+        lut = np.concatenate([[0], number[at:at + len(a)]]).astype(np.int32)
+        labels += lut[blobs]                      # the blobs of different values do not overlap
+        at += len(a)
+    return labels, value[order], area[order], first[order]
+
+
+def _props_host(labels, value, area, first, cap):
+    props = np.zeros((cap, 12), np.int64)
+    k = min(len(value), cap)
+    props[:k, 0], props[:k, 1], props[:k, 2] = value[:k], area[:k], first[:k]
+    flat = labels.reshape(-1)
+    idx = np.flatnonzero((flat > 0) & (flat <= k))
+    if not len(idx):
+        return props
+    order = np.argsort(flat[idx], kind='stable')  # the voxels blob by blob, every blob a run
+    idx = idx[order]
+    blob = flat[idx].astype(np.int64) - 1
+    starts = np.flatnonzero(np.concatenate([[True], blob[1:] != blob[:-1]]))
+    rows = blob[starts]
+    for axis, x in enumerate(np.unravel_index(idx, labels.shape)):
+        x = x.astype(np.int64)
+        props[rows, 3 + axis] = np.minimum.reduceat(x, starts)
+        props[rows, 6 + axis] = np.maximum.reduceat(x, starts) + 1
+        props[rows, 9 + axis] = np.add.reduceat(x, starts)
+    return props
+
+
+def label_components(volume, num_classes=None, props=False, max_blobs=65536):
+    """The label image of a volume and its region table: what the reference gets from skimage.measure.label(v, connectivity=1)
+    and regionprops (evalchaos_comparison_1cases.py:72-81).  volume: a 3-D integer volume of fewer than 2^31 voxels, any
+    strides.  num_classes=None: every voxel whose value is not 0 is a member; num_classes=C (2 .. 8): the values 1 .. C - 1
+    are, anything else is labelled 0.  Face neighbours of equal value are connected; the blobs of all values together are
+    numbered 1 .. n in raster order (C order of the logical index) of their first voxel.
+    -> (labels, count) or, with props=True, (labels, count, props): labels int32, contiguous, of the volume's shape, 0 on
+    non-members; count int64 [1], the true number of blobs; props int64 [max_blobs, 12], row j - 1 = (value, area, first raster
+    index, min0, min1, min2, max0 + 1, max1 + 1, max2 + 1, sum i0, sum i1, sum i2) of blob j: the box is half-open like
+    regionprops' bbox and the centroid is sum / area (`region_table` reads it).  Rows from count on are zero; with count >
+    max_blobs the labels and count are still complete and props holds the first max_blobs blobs.  max_blobs: 1 .. 2^20,
+    ValueError otherwise (and for any other num_classes) before a launch.  An empty volume gives empty labels, count 0 and
+    all-zero props.
+    HIP tensor: `aide_label_components3d`, seven launches, asynchronous, no host read, HIP tensors returned.  numpy array or CPU
+    tensor: scipy.ndimage.label once per value, numpy arrays returned."""
+    c = _post_classes(num_classes, 'label_components')
+    cap = _max_blobs(max_blobs)
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        _lcc_args(volume)
+        v = volume.detach()
+        if v.dtype != torch.int64:
+            v = v.to(torch.int64)
+        labels = torch.empty(v.shape, device=v.device, dtype=torch.int32)
+        count = torch.empty(1, device=v.device, dtype=torch.int64)
+        table = torch.empty(cap, 12, device=v.device, dtype=torch.int64) if props else None
+        ws = torch.empty(lib.aide_label_components3d_ws_bytes(v.numel()), device=v.device, dtype=torch.uint8)
+        check(lib.aide_label_components3d(ptr(v), *v.shape, *v.stride(), c or 0, ptr(labels), ptr(count), ptr(table), cap,
+                                          ptr(ws), stream_ptr()), 'label_components3d')
+        return (labels, count, table) if props else (labels, count)
+    vol = _host_volume(volume, 'label_components')
+    labels, value, area, first = _label_host(vol, c)
+    count = np.array([len(value)], np.int64)
+    if not props:
+        return labels, count
+    return labels, count, _props_host(labels, value, area, first, cap)
+
+
+def region_table(props, count):
+    """The host-side accessor of `label_components(..., props=True)`: one copy to the host, then a dict of numpy arrays over
+    the k = min(count, max_blobs) blobs the table holds: count (the true number of blobs, an int), value, area, first (int64
+    [k]), bbox (int64 [k, 6]: min0, min1, min2, max0 + 1, max1 + 1, max2 + 1, regionprops' order) and centroid (float64
+    [k, 3] = the coordinate sums / area)."""
+    if isinstance(props, torch.Tensor) or isinstance(count, torch.Tensor):
+        props = torch.as_tensor(props)
+        count = torch.as_tensor(count, device=props.device)
+        if props.dim() != 2 or props.shape[1] != 12 or count.numel() != 1:
+            raise TypeError('region_table: the props [max_blobs, 12] and the count [1] of label_components are expected')
+        both = torch.cat([count.reshape(1).to(torch.int64), props.reshape(-1).to(torch.int64)]).cpu().numpy()
+    else:
+        props, count = np.asarray(props), np.asarray(count)
+        if props.ndim != 2 or props.shape[1] != 12 or count.size != 1:
+            raise TypeError('region_table: the props [max_blobs, 12] and the count [1] of label_components are expected')
+        both = np.concatenate([count.reshape(1).astype(np.int64), props.reshape(-1).astype(np.int64)])
+    n, table = int(both[0]), both[1:].reshape(-1, 12)
+    table = table[:min(n, len(table))]
+    return dict(count=n, value=table[:, 0].copy(), area=table[:, 1].copy(), first=table[:, 2].copy(), bbox=table[:, 3:9].copy(),
+                centroid=table[:, 9:12].astype(np.float64) / table[:, 1:2].astype(np.float64))
+
+
+def _lesion_counts_host(pred, target, c, overlap):
+    """the host statement of aide_lesion_counts3d"""
+    out = np.zeros((c or 2, 6), np.int64)
+    for side, (a, b) in enumerate(((target, pred), (pred, target))):
+        labels, value, area, _ = _label_host(a, c)
+        agree = (labels > 0) & ((b == a) if c else (b != 0))
+        cover = np.bincount(labels[agree].astype(np.int64) - 1, minlength=len(value)).astype(np.int64)
+        counts = (cover >= 1) & (cover.astype(np.float64) >= overlap * area.astype(np.float64))
+        rows = value if c else np.ones(len(value), np.int64)
+        np.add.at(out[:, 2 * side], rows, 1)
+        np.add.at(out[:, 2 * side + 1], rows, counts.astype(np.int64))
+        if side == 0:
+            np.add.at(out[:, 4], rows, cover)
+        else:
+            np.add.at(out[:, 5], rows, np.where(counts, 0, area))
+    return out
+
+
+def lesion_counts(pred, target, num_classes=None, overlap=0.0):
+    """The table behind `lesion_scores`: int64 [rows, 6], rows = num_classes, or 2 with num_classes=None where row 1 is used;
+    row 0 is zeros.  Columns: target blobs, target blobs that count, pred blobs, pred blobs that count, the sum of cover over the
+    target blobs (the voxel-wise TP of the class), pred voxels in blobs that do not count.  A HIP tensor on either side:
+    `aide_lesion_counts3d` (ten launches, no host read), a HIP tensor returned; otherwise the host statement, a numpy array."""
+    c = _post_classes(num_classes, 'lesion_scores')
+    overlap = _overlap(overlap)
+    dev = [x for x in (pred, target) if isinstance(x, torch.Tensor) and x.is_cuda]
+    if dev:
+        p, t = (torch.as_tensor(x, device=dev[0].device).detach() for x in (pred, target))
+        _lcc_args(p)
+        _lcc_args(t)
+        if tuple(p.shape) != tuple(t.shape):
+            raise RuntimeError('lesion_scores: shape mismatch %s vs %s' % (tuple(p.shape), tuple(t.shape)))
+        p, t = (x if x.dtype == torch.int64 else x.to(torch.int64) for x in (p, t))
+        out = torch.empty(c or 2, 6, device=p.device, dtype=torch.int64)
+        ws = torch.empty(lib.aide_lesion_counts3d_ws_bytes(p.numel()), device=p.device, dtype=torch.uint8)
+        check(lib.aide_lesion_counts3d(ptr(p), *p.stride(), ptr(t), *t.stride(), *p.shape, c or 0, overlap, ptr(out), ptr(ws),
+                                       stream_ptr()), 'lesion_counts3d')
+        return out
+    p, t = _host_volume(pred, 'lesion_scores'), _host_volume(target, 'lesion_scores')
+    if p.shape != t.shape:
+        raise RuntimeError('lesion_scores: shape mismatch %s vs %s' % (p.shape, t.shape))
+    return _lesion_counts_host(p, t, c, overlap)
+
+
+def lesion_scores(pred, target, num_classes=None, overlap=0.0):
+    """Lesion-wise detection scores of a predicted label volume against its target.  Both volumes (3-D, the same shape, any
+    integer dtype and strides) are split into blobs by the rule of `label_components`.  For a blob b of one volume, cover(b) is
+    the number of voxels of b at which the other volume agrees: its voxel is not 0 (num_classes=None), or equals b's value
+    (num_classes=C).  b counts if and only if cover(b) >= 1 and float64(cover(b)) >= overlap * float64(area(b)); overlap is a
+    number in [0, 1] (ValueError otherwise) and the rule is the same on both sides, so swapping the arguments swaps the columns.
+    -> dict: the int64 counts target_blobs, detected (target blobs that count), pred_blobs, matched (pred blobs that count),
+    covered_voxels (the sum of cover over the target blobs: the voxel-wise TP), spurious_voxels (pred voxels in blobs that do
+    not count), and float64 sensitivity = detected / target_blobs, precision = matched / pred_blobs, F1 = 2 S P / (S + P) as
+    numpy true divisions (0/0 -> nan, like `case_scores`).  Scalars with num_classes=None, arrays of [C] with num_classes=C
+    (entry 0: zeros and nan).  HIP tensors: `aide_lesion_counts3d` and one copy of the table; anything else: the host statement
+    through scipy.ndimage.label."""
+    table = lesion_counts(pred, target, num_classes, overlap)
+    if isinstance(table, torch.Tensor):
+        table = table.cpu().numpy()
+    rows = table if num_classes is not None else table[1]
+    res = {name: (rows[:, k].copy() if num_classes is not None else int(rows[k])) for k, name in enumerate(LESION_COLUMNS)}
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f = np.asarray(rows, np.float64)
+        s, p = f[..., 1] / f[..., 0], f[..., 3] / f[..., 2]
+        res.update(sensitivity=s, precision=p, F1=2 * s * p / (s + p))
+    return res
 
 
 # ---- all cases of an epoch at once (the epoch end of trainchaos_proposed_30cases1labeled.py:429-496) ----------------

@@ -561,6 +561,43 @@ size_t aide_fill_holes3d_ws_bytes(int64_t nvox);
 int aide_fill_holes3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
                       int num_classes, int slice_axis, unsigned char* out, long long* stats /* NULL or [max(C, 2)][2] */,
                       void* ws, aide_stream_t stream);
+/* ---- labelled components and lesion-wise counts (the single volume) ----
+ * Members: num_classes = 0: every voxel whose value is not 0; num_classes = C in 2 .. 8: the values 1 .. C - 1.  Face neighbours
+ * of EQUAL value are connected (skimage.measure.label(v, connectivity=1)).  The blobs of all values together are numbered
+ * 1 .. n in raster order (C order of the logical index) of their first voxel. */
+/* workspace of aide_label_components3d (16-byte aligned): three int words per voxel (parent, area, rank), the control words and
+ * one int per 1024 voxels; 0 for nvox >= 2^31 */
+size_t aide_label_components3d_ws_bytes(int64_t nvox);
+/* labels[d0][d1][d2] (int32, contiguous) = the number of the voxel's blob, 0 for a voxel that is no member; count[0] (int64) =
+ * the number of blobs, always the true one.  props: NULL, or [max_blobs][12] int64 with max_blobs in 1 .. 2^20: row j - 1
+ * describes blob j as {value, area, raster index of the first voxel, min0, min1, min2, max0 + 1, max1 + 1, max2 + 1, sum i0,
+ * sum i1, sum i2} (a half-open box; centroid = sum / area); the rows from count on are zero, and with count > max_blobs the
+ * table holds the first max_blobs blobs while labels and count stay complete.
+ * Seven launches whatever the volume is: the three labelling launches of aide_keep_largest_cc3d, the rank of every root as a
+ * prefix sum over the root flags (per-block counts, a scan of the block counts by one workgroup, per-block ranks), one write;
+ * one memset when props is given.  Integer atomics only, no workgroup waits for another, no host read, the same bytes from call
+ * to call whatever the workspace held.  AIDE_ERR_ARG before any launch for num_classes outside {0, 2 .. 8}, d0 * d1 * d2 >= 2^31, a
+ * null count, props with max_blobs out of range, a null v / labels / ws or a misaligned ws; an empty volume launches nothing
+ * (count and props, when given, are cleared). */
+int aide_label_components3d(const long long* v, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                            int num_classes, int* labels, long long* count /* [1] */,
+                            long long* props /* NULL or [max_blobs][12] */, int64_t max_blobs, void* ws, aide_stream_t stream);
+/* workspace of aide_lesion_counts3d (16-byte aligned): three int words per voxel (parent, area, cover) that the two volumes use
+ * one after the other, and the control words; 0 for nvox >= 2^31 */
+size_t aide_lesion_counts3d_ws_bytes(int64_t nvox);
+/* Both volumes (int64, logical shape (d0, d1, d2), element strides each) are labelled by the rule above.  For a blob b of one
+ * volume, cover(b) = the voxels of b at which the OTHER volume agrees: its voxel is not 0 (num_classes = 0), or equals b's value
+ * (num_classes = C).  b counts if and only if cover(b) >= 1 and (double)cover(b) >= overlap * (double)area(b), overlap in [0, 1].
+ * out[rows][6] int64, rows = C (row c: the blobs of value c) or 2 (num_classes = 0: row 1), row 0 zeros: {target blobs, target
+ * blobs that count, pred blobs, pred blobs that count, sum of cover over the target blobs (= the voxel-wise TP of the class),
+ * pred voxels in blobs that do not count}.  Swapping pred and target swaps columns 0 - 1 with 2 - 3.
+ * Ten launches (per volume the three labelling launches, cover, reduce) and three memsets whatever the volumes are; integer
+ * atomics, one double multiply and compare per blob, no host read.  AIDE_ERR_ARG before any launch for num_classes outside
+ * {0, 2 .. 8}, overlap outside [0, 1], d0 * d1 * d2 >= 2^31, a null out, and on a volume that is not empty a null pred / target /
+ * ws or a misaligned ws; an empty volume clears out and launches nothing. */
+int aide_lesion_counts3d(const long long* pred, int64_t p_s0, int64_t p_s1, int64_t p_s2, const long long* target,
+                         int64_t t_s0, int64_t t_s1, int64_t t_s2, int64_t d0, int64_t d1, int64_t d2, int num_classes,
+                         double overlap, long long* out /* [max(C, 2)][6] */, void* ws, aide_stream_t stream);
 /* out[4] (int64) = {N, sum p*t, sum p, sum t} over the logical volume; p / t are int64 (x_u8 = 0) or uint8 (x_u8 = 1)
  * with element strides.  TP = out[1], FP = out[2] - out[1], FN = out[3] - out[1], TN = N - out[2] - out[3] + out[1] */
 int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
