@@ -7,6 +7,8 @@
 // the float bits, ties by lower index like a stable argsort) that also sums a second array over the selected
 // set in fp64, and the max-pooled region cross entropy with its scatter backward.  HBM-bound streaming kernels;
 // no atomics on floating-point data, so results are bit-reproducible.
+// Targets outside [0, C): two classes take every non-zero target as class 1 (packed region CE, droppixel, pixelcoreg); the
+// C-class and window region-CE kernels ignore the region; the C-class droppixel kernels keep the KL term and drop the CE term.
 #include "common.h"
 
 namespace {
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256) void region_ce_win_kernel(const float* __restr
         long long tp = t[n * tb + h0 * W + w0];
         for (int hh = h0; hh < h1; ++hh)
             for (int ww = w0; ww < w1; ++ww) { const long long v = t[n * tb + hh * W + ww]; tp = v > tp ? v : tp; }
-        const bool ign = tp == ignore_index;
+        const bool ign = tp == ignore_index || tp < 0 || tp >= C;
         float l = 0.f;
         if (!ign) {                                   // lse(m) - m[tp], the arithmetic of log_softmax + nll_loss
             float mx = m[0];
@@ -308,8 +310,9 @@ __global__ __launch_bounds__(256) void region_ce_win_bwd_kernel(const float* __r
 
 // ---------------------------------------------------------------- k smallest of a segment (+ sum of a second array)
 __device__ __forceinline__ unsigned fkey(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);     // total order of floats as unsigned keys
+    if (v != v) return 0xffffffffu;                         // any NaN, either sign: last, like argsort
+    const unsigned b = v == 0.0f ? 0u : __float_as_uint(v); // -0.0 == +0.0: one key, the tie goes by index
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);     // order of floats as unsigned keys
 }
 
 // One workgroup (1024 threads) per segment of M values.  Candidates: all values, or only those > 0.
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(256) void droppixel_map_kernel(const float* __restr
     }
 }
 
-// g1/g2 [N][2][HW] (pre-zeroed): += coeff * mask * d v / d logits on the images idx[m]
+// g1/g2 [N][2][HW] (pre-zeroed): coeff * mask * d v / d logits stored on the images idx[m]; other images are not written
 __global__ __launch_bounds__(256) void droppixel_bwd_kernel(const float* __restrict__ z1, long b1,
                                                             const float* __restrict__ z2, long b2,
                                                             const long long* __restrict__ t, long tb,
