@@ -12,6 +12,16 @@
 // larger (concatenation) buffer; this is how torch.cat is eliminated (fuseunet.py:49, netblocks.py:145).
 // Reductions: fp64 accumulation per thread -> fixed-order tree -> per-(channel,split) partials ->
 // finalize in channel order.  No atomics: results are bit-reproducible run to run.
+//
+// One arithmetic for every form.  The one-pass and the two-pass kernels, at every unit width and storage type, sum the SAME float64
+// terms from the first value on -- z and z * z in the forward pass; dy, dy * xhat (the exact product of the two fp32 values) and xhat
+// in the backward pass -- and evaluate the same fp32 expressions per element.  Storage changes no term (widening bf16 is exact), so a
+// call on bf16-stored tensors returns the statistics, coefficient vectors and gradient sums of the fp32 call on the widened tensors
+// bit for bit, and its outputs are that call's outputs rounded to nearest even: within one form because the partition is the same, and
+// between forms (a bf16-stored tensor of 9 Mi .. 34 Mi values takes two passes where the fp32 call takes one, coop_plan) because the
+// forms differ in the association of float64 sums alone, n * 2^-53 of the sum of magnitudes, which the rounding to fp32 hides.  (The
+// two-pass kernels used to add every V values in fp32 first: their dgamma was up to two fp32 spacings away from the one-pass value.)
+// Held by tests/test_gpu_bn_paths.py::test_storage_combinations (all 4 forward and 8 backward storage combinations on four paths).
 #include "common.h"
 #include <type_traits>
 
@@ -157,14 +167,12 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const ZT* __restrict__ z,
         } else {
             ldv<V>(zc + (long)cur.n * z_bs + cur.p * V, v);
         }
-        float s1 = 0.0f;                           // the V-element group sum in fp32, promoted once (squares stay fp64:
-#pragma unroll                                     // E[z^2] - mean^2 cancels)
+#pragma unroll                                     // float64 from the first value on, as bn_fwd_coop_kernel (rule at the top of the file)
         for (int k = 0; k < V; ++k) {
             const double d = (double)v[k];
-            s1 += v[k];
+            acc[0] += d;
             acc[1] = fma(d, d, acc[1]);
         }
-        acc[0] += (double)s1;
     }
     block_sum_d<2>(acc, sm);
     if (threadIdx.x == 0) {
@@ -371,19 +379,15 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const GT* __restrict
         float zv[V], dv[V];
         ldv<V>(zc + (long)cur.n * z_bs + cur.p * V, zv);
         ldv<V>(dc + (long)cur.n * d_bs + cur.p * V, dv);
-        float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;     // V-element group sums in fp32, promoted once per group
-#pragma unroll
+#pragma unroll                                     // float64 from the first value on, as bn_bwd_coop_kernel (rule at the top of the file)
         for (int k = 0; k < V; ++k) {
             const bool on = !relu || fmaf(zv[k], sc, sh) > 0.0f;
             const float dy = on ? dv[k] : 0.0f;
             const float xh = (zv[k] - mu) * rs;
-            t0 += dy;
-            t1 = fmaf(dy, xh, t1);
-            t2 += xh;
+            acc[0] += (double)dy;
+            acc[1] = fma((double)dy, (double)xh, acc[1]);
+            acc[2] += (double)xh;
         }
-        acc[0] += (double)t0;
-        acc[1] += (double)t1;
-        acc[2] += (double)t2;
     }
     block_sum_d<3>(acc, sm);
     if (threadIdx.x == 0) {

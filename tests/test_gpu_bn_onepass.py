@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bn_cases as B
+
 pytestmark = pytest.mark.gpu
 
 
@@ -84,10 +86,17 @@ def test_onepass_fwd_bwd_vs_aten(dev, shape):
     dz = torch.empty_like(zd)
     dg, db, dbias = (torch.empty(c, device=dev) for _ in range(3))
     ops.bn_relu_bwd(dAd, zd, dz, mean, rstd, scale, shift, dg, db, dbias, ws, True)
-    # (the ReLU mask of an element within rounding of zero may differ from the float64 reference: compare where it agrees)
+    # (the ReLU mask of an element within rounding of zero may differ from the float64 reference)
     mask_ref = (ar > 0).cpu()
     mask_got = (a > 0).cpu()
     assert (mask_ref != mask_got).sum().item() <= 2
+    # ... so the backward is ALWAYS held to the kernel's contract in float64 under the device's own coefficients, whose mask is the
+    # kernel's mask exactly (bn_cases.ref_contract), and to autograd as well where the two masks agree
+    r2 = B.ref_contract(zd, dAd, mean, rstd, scale, shift)
+    assert torch.equal(r2['mask'], a > 0)
+    _close(dz, r2['dz'], rtol=5e-5, what='dz vs contract')
+    _close(dg, r2['dgamma'], rtol=5e-5, what='dgamma vs contract')
+    _close(db, r2['dbeta'], rtol=5e-5, what='dbeta vs contract')
     if torch.equal(mask_ref, mask_got):
         _close(dz, zr.grad, rtol=5e-5, what='dz')
         _close(dg, bn.weight.grad, rtol=5e-5, what='dgamma')
@@ -301,6 +310,15 @@ def test_onepass_bwd_with_pooled_gradient(dev, shape):
     ar = F.relu(bn(zr))
     (F.max_pool2d(ar, 2) * pdy.cpu().double()).sum().backward(retain_graph=True)
     (ar * dA.cpu().double()).sum().backward()
+    # always: the contract in float64 under the device's coefficients (bn_cases.ref_contract: its mask is the kernel's mask) on
+    # dA + aten's max-pooling gradient of the device's own activation (the first maximum of a window takes it)
+    at = a.detach().cpu().requires_grad_(True)
+    (F.max_pool2d(at, 2) * pdy.cpu()).sum().backward()
+    r2 = B.ref_contract(z, dA.double() + at.grad.to(dev).double(), st[0], st[1], st[2], st[3])
+    assert torch.equal(r2['mask'], a > 0)
+    _close(out[0], r2['dz'], rtol=1e-4, what='dz vs contract')
+    _close(out[1], r2['dgamma'], rtol=1e-4, what='dgamma vs contract')
+    _close(out[2], r2['dbeta'], rtol=1e-4, what='dbeta vs contract')
     if torch.equal((ar > 0).cpu(), (a > 0).cpu()):
         _close(out[0], zr.grad, rtol=1e-4, what='dz vs autograd')
 
