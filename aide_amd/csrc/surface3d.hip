@@ -26,6 +26,10 @@
 // with launch 4 as surf_minplus<true, true>, which also appends every distance to a per-operand list of uint64 keys, and then
 // 8 x (sel_hist, sel_choose): an exact MSD radix select over those lists for all (set, rank) targets at once -- see there.
 // Integer atomics only; the lists' order depends on the schedule and nothing computed from them does.
+//
+// aide_edt3d (the distance transform of one volume, every voxel evaluated) runs launches 2 and 3 on one operand whose
+// candidates are its background voxels, between a launch that writes that map and edt_last, the walk along d0 with the square
+// root -- see there.
 #include "common.h"
 
 #include <cmath>
@@ -391,6 +395,58 @@ __global__ __launch_bounds__(256) void sel_choose_kernel(SelArgs a, SelState* __
     }
 }
 
+// ---- the full distance transform of one volume (aide_edt3d) ---------------------------------------------------------------------
+// Candidates are the voxels that are NOT foreground.  Launches: edt_bg (the candidate map as bytes in logical raster order; from
+// here on no stride is read), surf_scan2 and surf_minplus<false> as above with one operand, edt_last.
+__global__ __launch_bounds__(256) void edt_bg_kernel(Operand X, int d1, int d2, int n, int cls, unsigned char* __restrict__ bmap) {
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (unsigned)n) return;
+    const int i = (int)u, plane = d1 * d2, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
+    bmap[i] = !fg_at(X, (long)i0 * X.s0 + (long)i1 * X.s1 + (long)i2 * X.s2, cls);
+}
+
+// the walk of surf_minplus<true> along d0 on f of the same operand, evaluated at every voxel: dist = sqrt(min).  A candidate is
+// its own nearest (min = 0, dist = 0 on the background); without any candidate every f is +inf and so is every dist.
+__global__ __launch_bounds__(256) void edt_last_kernel(Lines q, const double* __restrict__ f, double* __restrict__ dist) {
+    __shared__ double h[CH][COLS];
+    const int col = threadIdx.x & 63, row = threadIdx.x >> 6;
+    const long c = (long)blockIdx.x * COLS + col;
+    const bool live = c < q.ncol;
+    const size_t start = live ? (size_t)c : 0;
+    const double inf = __builtin_inf();
+    for (int o0 = 0; o0 < q.L; o0 += OC) {
+        const int first = o0 + row * R;
+        double best[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) best[r] = inf;
+        for (int j0 = 0; j0 < q.L; j0 += CH) {
+            __syncthreads();                     // the previous chunk is read to the end
+#pragma unroll
+            for (int k = 0; k < CH / ROWS; ++k) {
+                const int jl = k * ROWS + row, j = j0 + jl;
+                h[jl][col] = live && j < q.L ? f[start + (size_t)j * q.stride] : inf;
+            }
+            __syncthreads();
+            double dd = (double)(first - j0);    // result index - candidate index, exact
+#pragma unroll 4
+            for (int jl = 0; jl < CH; ++jl) {
+                const double hv = h[jl][col];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double t = q.sp * (dd + (double)r);
+                    best[r] = fmin(best[r], t * t + hv);
+                }
+                dd -= 1.0;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = first + r;
+            if (live && i < q.L) dist[start + (size_t)i * q.stride] = sqrt(best[r]);
+        }
+    }
+}
+
 bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
     if (d0 < 0 || d1 < 0 || d2 < 0) return false;
     if (d0 == 0 || d1 == 0 || d2 == 0) return true;
@@ -534,6 +590,51 @@ int aide_surface3d_scores_select(const void* p, int p_u8, int64_t p_s0, int64_t 
     }
     return surface_run(p, p_u8, p_s0, p_s1, p_s2, t, t_u8, t_s0, t_s1, t_s2, d0, d1, d2, sp0, sp1, sp2, cls, &a, out, dist, ws,
                        stream);
+}
+
+// g [n] int32 | f [n] fp64 | candidate map [n] bytes
+size_t aide_edt3d_ws_bytes(int64_t nvox) {
+    if (nvox < 0 || nvox > INT32_MAX) return 0;
+    const size_t n = (size_t)nvox;
+    return align16(n * sizeof(double)) + align16(n * sizeof(int)) + align16(n) + 16;
+}
+
+int aide_edt3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2, int cls,
+               const double* spacing, double* dist, void* ws, hipStream_t stream) {
+    if (!dims_ok(d0, d1, d2) || !spacing || (v_u8 != 0 && v_u8 != 1)) return AIDE_ERR_ARG;
+    const double sp0 = spacing[0], sp1 = spacing[1], sp2 = spacing[2];
+    if (!(sp0 > 0.0 && sp1 > 0.0 && sp2 > 0.0) || !std::isfinite(sp0) || !std::isfinite(sp1) || !std::isfinite(sp2))
+        return AIDE_ERR_ARG;
+    const int n = (int)(d0 * d1 * d2);
+    if (n == 0) return 0;
+    if (!v || !dist || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0 || (reinterpret_cast<uintptr_t>(dist) & 7) != 0 ||
+        (!v_u8 && (reinterpret_cast<uintptr_t>(v) & 7) != 0))
+        return AIDE_ERR_ARG;
+    const int plane = (int)(d1 * d2), lines = (int)(d0 * d1);
+    const long cols1 = (long)d0 * d2;
+    char* w = static_cast<char*>(ws);
+    double* f = reinterpret_cast<double*>(w);
+    w += align16((size_t)n * sizeof(double));
+    int* g = reinterpret_cast<int*>(w);
+    w += align16((size_t)n * sizeof(int));
+    unsigned char* bmap = reinterpret_cast<unsigned char*>(w);
+    const Operand X{v, (long)s0, (long)s1, (long)s2, v_u8};
+    Lines a1, a0;
+    a1.L = (int)d1; a1.stride = (int)d2; a1.inner = (int)d2; a1.outer = plane; a1.ncol = (int)cols1; a1.n = n;
+    a1.sp = sp1; a1.sp_in = sp2;
+    a0.L = (int)d0; a0.stride = plane; a0.inner = plane; a0.outer = 0; a0.ncol = plane; a0.n = n;
+    a0.sp = sp0; a0.sp_in = 0.0;
+    const dim3 block(256);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (double)n * (v_u8 ? 2 : 9), edt_bg_kernel, dim3((unsigned)(((long)n + 255) / 256)), block, 0,
+                      stream, X, (int)d1, (int)d2, n, cls, bmap);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 5.0 * n, surf_scan2_kernel, dim3((unsigned)((lines + 255) / 256), 1), block, 0, stream,
+                      (const unsigned char*)bmap, lines, (int)d2, n, g);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 12.0 * n, surf_minplus_kernel<false>, dim3((unsigned)((cols1 + COLS - 1) / COLS), 1), block,
+                      0, stream, a1, (const int*)g, f, (const unsigned char*)nullptr, (double*)nullptr, (double*)nullptr,
+                      (unsigned long long*)nullptr, (unsigned*)nullptr);
+    AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 16.0 * n, edt_last_kernel, dim3((unsigned)((plane + COLS - 1) / COLS)), block, 0, stream, a0,
+                      (const double*)f, dist);
+    return aide_launch_status();
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@ from .ensemble import (VIEW_SETS, view_codes, view_apply_host, view_invert_host,
                        ensemble_vote_host, ensemble_logits, predict_ensemble)
 from .window import (window_grid, window_weights, window_stack, window_blend, window_blend_host,  # noqa: F401
                      predict_windows)
+from .morphology import ball, erode, dilate, open_, close, distance_transform  # noqa: F401
 
 
 def label_map(logits):
@@ -99,7 +100,11 @@ def predict_case(net, *modal_inputs, **kw):
     one per class, sequences allowed); TypeError when keep_largest is False.  fill_holes=True: `fill_holes` after the filter, on
     its uint8 output, binary or per class as the filter is (keep_largest=False: binary unless num_classes is given), along
     slice_axis= when given (2 is the slice axis of the [H,W,S] volume).  With all four at their defaults every call takes the
-    path it took before."""
+    path it took before.
+    opening=r / closing=r (millimetres, with spacing=(sp_h, sp_w, sp_s), default 1 mm cubes; aide_amd/morphology.py): `open_`
+    with the ball of radius r on the labels before the filter, `close` after fill_holes; both per class exactly when the filter
+    is (keep_largest='per_class', or num_classes with no filter), binary otherwise.  spacing without either: TypeError.  With
+    both at their defaults every call takes the path it took before."""
     keep_largest = kw.pop('keep_largest', False)
     want_probs = kw.pop('probs', False)
     num_classes = kw.pop('num_classes', None)
@@ -108,6 +113,12 @@ def predict_case(net, *modal_inputs, **kw):
     min_voxels = kw.pop('min_voxels', _UNSET)
     fill = kw.pop('fill_holes', False)
     slice_axis = kw.pop('slice_axis', None)
+    opening = kw.pop('opening', None)
+    closing = kw.pop('closing', None)
+    spacing = kw.pop('spacing', None)
+    morph = opening is not None or closing is not None
+    if spacing is not None and not morph:
+        raise TypeError('predict_case: spacing goes with opening / closing')
     per_class = isinstance(keep_largest, str)
     if per_class:
         if keep_largest != 'per_class':
@@ -115,8 +126,8 @@ def predict_case(net, *modal_inputs, **kw):
         if num_classes is None:
             raise TypeError("predict_case: keep_largest='per_class' needs num_classes")
         num_classes = _num_classes(num_classes, 'predict_case')
-    elif num_classes is not None and (keep_largest or not fill):
-        raise TypeError("predict_case: num_classes goes with keep_largest='per_class' (or with fill_holes and no filter)")
+    elif num_classes is not None and (keep_largest or not (fill or morph)):
+        raise TypeError("predict_case: num_classes goes with keep_largest='per_class' (or with fill_holes / opening / closing and no filter)")
     ranked = top_k is not _UNSET or min_voxels is not _UNSET
     if ranked and not keep_largest:
         raise TypeError('predict_case: top_k / min_voxels go with keep_largest')
@@ -138,6 +149,8 @@ def predict_case(net, *modal_inputs, **kw):
         vol = vol.permute(1, 2, 0)
     else:
         vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)
+    if opening is not None:
+        vol = open_(vol, opening, (1.0, 1.0, 1.0) if spacing is None else spacing, num_classes)
     if ranked:
         vol = keep_components(vol, 1 if top_k is _UNSET else top_k, 1 if min_voxels is _UNSET else min_voxels,
                               num_classes if per_class else None)
@@ -147,6 +160,8 @@ def predict_case(net, *modal_inputs, **kw):
         vol = keep_largest_connected_components(vol)
     if fill:
         vol = fill_holes(vol, num_classes, slice_axis)
+    if closing is not None:
+        vol = close(vol, closing, (1.0, 1.0, 1.0) if spacing is None else spacing, num_classes)
     if not as_numpy:
         return vol if pr is None else (vol, pr)
     vol = vol.contiguous().cpu().numpy()

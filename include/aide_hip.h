@@ -656,6 +656,44 @@ int aide_surface3d_scores_select(const void* p, int p_u8, int64_t p_s0, int64_t 
                                  int cls, const double* q, int nq, const double* tol, int nt,
                                  void* out, double* dist, void* ws, aide_stream_t stream);
 
+/* ---- the Euclidean distance transform of one volume, and ball morphology in millimetres.  v as in aide_fill_holes3d (int64,
+ * v_u8 = 0, or uint8, v_u8 = 1; logical shape (d0, d1, d2), element strides); spacing = HOST array of the three edge lengths
+ * of a voxel along the logical dims, read before the call returns.  Squared length of an integer offset o, in fp64 and in
+ * exactly this association (the order in which the passes along d2, d1, d0 accumulate):
+ *     q(o) = (sp0 * o0)^2 + ((sp1 * o1)^2 + (sp2 * o2)^2)
+ * (sp_k * d_k)^2 must stay finite. */
+/* workspace of aide_edt3d (16-byte aligned): f [n] fp64 | g [n] int32 | candidate map [n] bytes; 0 for nvox >= 2^31 */
+size_t aide_edt3d_ws_bytes(int64_t nvox);
+/* Foreground: v != 0 (cls < 0) or v == cls.  dist[d0][d1][d2] (fp64, contiguous) = 0 on the background and
+ * sqrt(min over background u of q(v - u)) on the foreground (scipy.ndimage.distance_transform_edt(fg, sampling=spacing));
+ * +inf everywhere when the volume has no background voxel.  Four launches: the background map in raster order, the scan
+ * along d2 and the min-plus walk along d1 of aide_surface3d_scores, the walk along d0 with the square root at every voxel.
+ * No atomic, no workgroup waits for another, every workspace word that is read was written by the same call.  AIDE_ERR_ARG
+ * before any launch for d0 * d1 * d2 >= 2^31, a null spacing, a spacing that is not positive and finite, v_u8 outside {0, 1},
+ * and on a volume that is not empty a null v / dist / ws, a ws off 16 bytes, a dist or an int64 v off 8 bytes; an empty volume
+ * launches nothing. */
+int aide_edt3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2, int cls,
+               const double* spacing /* host [3] */, double* dist, void* ws, aide_stream_t stream);
+/* workspace of aide_morph3d (16-byte aligned): f [n] fp64 | g [n] int32 | class map [n] bytes | the plane between the two
+ * primitives of an opening or closing [n] bytes; 0 for nvox >= 2^31 */
+size_t aide_morph3d_ws_bytes(int64_t nvox);
+/* Ball B(r) = {o : q(o) <= radius * radius}.  op: 0 erosion with the outside of the volume as background, 1 erosion with the
+ * outside as foreground, 2 dilation, 3 opening = dilate(erode0), 4 closing = erode1(dilate) (extensive).
+ * num_classes = 0: X = (v != 0), out[d0][d1][d2] (uint8, contiguous) = 0 / 1.  num_classes = C in 2 .. 8: every plane
+ * X_c = (v == c), c in 1 .. C - 1, is transformed on its own; erosion / opening: out = c where plane c survives, else 0;
+ * dilation / closing: a voxel with v in 1 .. C - 1 keeps v, any other voxel becomes c when exactly one class claims it and 0
+ * when none or several do.  A value outside 0 .. C - 1 belongs to no class.
+ * Along axis k only the W_k = floor(radius / sp_k) nearest candidates on either side are evaluated.  Launches: one that reads
+ * the strided volume into the class map, then per class 1 .. C - 1 (once for num_classes = 0) three (scan along d2, min-plus
+ * along d1, min-plus along d0 with the compare) for op 0 - 2 and six for op 3 - 4; one memset (op 0, 1, 3).  One thread per
+ * voxel in every launch, no atomic, no workgroup waits for another, no host read, every workspace word that is read was
+ * written by the same call: two calls give the same bytes.  AIDE_ERR_ARG before any launch for num_classes outside
+ * {0, 2 .. 8}, an unknown op, a radius that is negative or not finite, and everything aide_edt3d rejects (out for dist, no
+ * alignment asked of out); an empty volume launches nothing. */
+int aide_morph3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                 int num_classes, int op, double radius, const double* spacing /* host [3] */, unsigned char* out, void* ws,
+                 aide_stream_t stream);
+
 /* ---- the same for all cases of an epoch at once: K ragged cases concatenated as [S_total][H][W] (contiguous; what the
  * label map yields when fed all slices) with a DEVICE table slice_start[K + 1] (int64, non-decreasing, slice_start[0] >= 0,
  * slice_start[K] <= S_total; an entry outside that is clamped so that no access leaves the buffers).  Case k's logical
