@@ -38,13 +38,13 @@ def _digest(paths):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    common = os.path.join(CSRC, 'common.h')
+    headers = [os.path.join(CSRC, h) for h in ('common.h', 'volume3d.h')]
 
     def compile_one(src):
         sp = os.path.join(CSRC, src)
         op = os.path.join(OBJ, src.replace('.hip', '.o'))
         stamp = op + '.sha1'
-        dg = _digest([sp, common])
+        dg = _digest([sp] + headers)
         if not force and os.path.exists(op) and os.path.exists(stamp) and open(stamp).read() == dg:
             return op, False
         cmd = [hipcc] + FLAGS + ['-c', sp, '-o', op]

@@ -58,7 +58,7 @@
 //                          the other (parent, area, cover).  Ten launches and three memsets (the table, cover twice).  The
 //                          one non-integer operation of the file is its threshold: double(cover) >= overlap * double(area)
 // In all of them no workgroup ever waits for another.
-#include "common.h"
+#include "volume3d.h"
 
 namespace {
 
@@ -71,6 +71,12 @@ struct View {
     int base;             // node of voxel (0, 0, 0); node of (i0, i1, i2) = base + raster index
     __device__ __forceinline__ bool has(int i0, int i1, int i2) const { return i0 < d0 && i1 < d1 && i2 < d2; }
     __device__ __forceinline__ long off(int i0, int i1, int i2) const { return (long)i0 * s0 + (long)i1 * s1 + (long)i2 * s2; }
+    __device__ __forceinline__ void decode(int i, int& i0, int& i1, int& i2) const { raster_decode(i, d1, d2, i0, i1, i2); }
+    __device__ __forceinline__ long off_of(int i) const {   // of raster index i
+        int i0, i1, i2;
+        decode(i, i0, i1, i2);
+        return off(i0, i1, i2);
+    }
     __device__ __forceinline__ int node(int i0, int i1, int i2) const { return base + (i0 * d1 + i1) * d2 + i2; }
 };
 
@@ -106,10 +112,7 @@ struct Strided {
     // decoded from the node only where it is needed.  Select is grid-strided over the nodes, write has one node per thread
     template <class F>
     __device__ void visit(const View& g, int i, F& f) const {
-        f(g.base + i, [&] {
-            const int plane = g.d1 * g.d2, i0 = i / plane, r = i - i0 * plane, i1 = r / g.d2;
-            return g.off(i0, i1, r - i1 * g.d2);
-        }, (long)i);
+        f(g.base + i, [&] { return g.off_of(i); }, (long)i);
     }
     template <class F>
     __device__ void select_nodes(const View& g, F f) const {
@@ -648,8 +651,9 @@ __global__ __launch_bounds__(256) void holes_flag_kernel(Strided geo, Background
     if (u >= (unsigned)(g.d0 * g.d1 * g.d2)) return;
     const int i = (int)u, p = parent[i];
     if (p < 0) return;
-    const int plane = g.d1 * g.d2, i0 = i / plane, rem = i - i0 * plane, i1 = rem / g.d2;
-    const int x[3] = {i0, i1, rem - i1 * g.d2}, d[3] = {g.d0, g.d1, g.d2};
+    int x[3];
+    g.decode(i, x[0], x[1], x[2]);
+    const int d[3] = {g.d0, g.d1, g.d2};
     const long st[3] = {g.s0, g.s1, g.s2}, off = g.off(x[0], x[1], x[2]);
     unsigned bits = 0;
 #pragma unroll
@@ -683,8 +687,8 @@ __global__ __launch_bounds__(256) void holes_write_kernel(Strided geo, Backgroun
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     int fc = 0, fa = 0;                           // class and area of a filled blob whose root this thread holds
     if (u < (unsigned)(g.d0 * g.d1 * g.d2)) {
-        const int i = (int)u, plane = g.d1 * g.d2, i0 = i / plane, rem = i - i0 * plane, i1 = rem / g.d2;
-        const long long v = (long long)bg.raw(g, g.off(i0, i1, rem - i1 * g.d2));
+        const int i = (int)u;
+        const long long v = (long long)bg.raw(g, g.off_of(i));
         int o;
         if (v != 0) {
             o = C ? class_of(v, C) : 1;
@@ -727,22 +731,14 @@ __device__ __forceinline__ long long block_sum3(long long s0, long long s1, long
     return sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
 }
 
-struct Operand {
-    const void* p;
-    long s0, s1, s2;
-};
-
 template <typename TP, typename TT>
 __global__ __launch_bounds__(256) void confusion_kernel(Operand P, Operand T, int d1, int d2, int n,
                                                         long long* __restrict__ out) {
-    const TP* pp = static_cast<const TP*>(P.p);
-    const TT* tp = static_cast<const TT*>(T.p);
-    const int plane = d1 * d2;
     long long spt = 0, sp = 0, st = 0;
     for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < (unsigned)n; u += gridDim.x * 256u) {
-        const int i = (int)u, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
-        const long long a = (long long)pp[(long)i0 * P.s0 + (long)i1 * P.s1 + (long)i2 * P.s2];
-        const long long b = (long long)tp[(long)i0 * T.s0 + (long)i1 * T.s1 + (long)i2 * T.s2];
+        int i0, i1, i2;
+        raster_decode((int)u, d1, d2, i0, i1, i2);
+        const long long a = P.at<TP>(P.off(i0, i1, i2)), b = T.at<TT>(T.off(i0, i1, i2));
         spt += a * b; sp += a; st += b;
     }
     const long long s = block_sum3(spt, sp, st);
@@ -797,19 +793,7 @@ __global__ __launch_bounds__(256) void confusion_batched_kernel(const unsigned c
 constexpr int SCAN = 1024;
 constexpr int PROPS = 12;                         // value, area, first, min0..2, max0..2 + 1, sum0..2
 
-__device__ __forceinline__ void node_coords(const View& g, int i, int& i0, int& i1, int& i2) {
-    const int plane = g.d1 * g.d2;
-    i0 = i / plane;
-    const int r = i - i0 * plane;
-    i1 = r / g.d2;
-    i2 = r - i1 * g.d2;
-}
-
-__device__ __forceinline__ long long node_value(const View& g, int i) {
-    int i0, i1, i2;
-    node_coords(g, i, i0, i1, i2);
-    return g.v[g.off(i0, i1, i2)];
-}
+__device__ __forceinline__ long long node_value(const View& g, int i) { return g.v[g.off_of(i)]; }
 
 // 0: node u is no root (or lies past the volume), 1: a member root, -1: the root of a blob of another value
 __device__ __forceinline__ int root_kind(const View& g, const int* __restrict__ parent, unsigned u, unsigned n, int C) {
@@ -902,7 +886,7 @@ __global__ __launch_bounds__(256) void lab_rank_kernel(Strided geo, const int* _
         rank[i] = j;
         if (props && j >= 0 && j < cap) {
             int i0, i1, i2;
-            node_coords(g, i, i0, i1, i2);
+            g.decode(i, i0, i1, i2);
             long long* row = props + (long)j * PROPS;
             row[0] = g.v[g.off(i0, i1, i2)]; row[1] = area[i]; row[2] = i;
             row[3] = i0; row[4] = i1; row[5] = i2;
@@ -986,7 +970,7 @@ __global__ __launch_bounds__(256) void lab_write_kernel(Strided geo, const int* 
         unsigned long long pending = __ballot(add);
         if (!pending) continue;
         int x0 = 0, x1 = 0, x2 = 0;
-        if (add) node_coords(g, (int)((blockIdx.x * (unsigned)WRITE_K + k) * 256u + threadIdx.x), x0, x1, x2);
+        if (add) g.decode((int)((blockIdx.x * (unsigned)WRITE_K + k) * 256u + threadIdx.x), x0, x1, x2);
         while (pending) {
             const int leader = __ffsll((long long)pending) - 1;
             const int jl = __shfl(j, leader);
@@ -1049,8 +1033,8 @@ __global__ __launch_bounds__(256) void les_cover_kernel(Strided geo, Operand B, 
             const int i = (int)u, p = parent[i];
             if (p >= 0) {
                 int i0, i1, i2;
-                node_coords(g, i, i0, i1, i2);
-                const long long b = static_cast<const long long*>(B.p)[(long)i0 * B.s0 + (long)i1 * B.s1 + (long)i2 * B.s2];
+                g.decode(i, i0, i1, i2);
+                const long long b = B.at<long long>(B.off(i0, i1, i2));
                 bool agree = b != 0;
                 if (C) {
                     const long long a = g.v[g.off(i0, i1, i2)];
@@ -1120,12 +1104,6 @@ __global__ __launch_bounds__(256) void les_reduce_kernel(Strided geo, const int*
 }
 
 // ---- host ----
-bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
-    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
-    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
-}
-
 // [S_total][H][W] with K cases: everything the grids and the node indices need fits an int
 bool batch_ok(int64_t S_total, int64_t H, int64_t W, int64_t K) {
     if (S_total < 0 || H < 0 || W < 0 || K < 0 || K > 65535) return false;
@@ -1180,10 +1158,10 @@ template <class G>
 int lcc_launch(const G& geo, const Grids& gr, int n, int64_t K, int C, unsigned char* out, long long* stats, void* ws,
                hipStream_t stream) {
     if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
-    int* parent = static_cast<int*>(ws);
+    Carver carver(ws);
+    int* parent = carver.take<int>(2 * (size_t)n);
     int* area = parent + n;
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(area + n) + 15) & ~static_cast<uintptr_t>(15));
+    unsigned long long* ctrl = carver.take<unsigned long long>(0);
     const int* cparent = parent;
     const int* carea = area;
     const unsigned long long* cctrl = ctrl;
@@ -1213,9 +1191,9 @@ struct Carved {
     unsigned long long* ctrl;
 };
 Carved carve(void* ws, int n) {
-    int* parent = static_cast<int*>(ws);
-    return Carved{parent, parent + n, reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(parent + 2 * (size_t)n) + 15) & ~static_cast<uintptr_t>(15))};
+    Carver c(ws);
+    int* parent = c.take<int>(2 * (size_t)n);
+    return Carved{parent, parent + n, c.take<unsigned long long>(0)};
 }
 
 // k largest with a floor: memset(s), launches 1 - 3, `passes` select passes, write; C = 0: BINARY
@@ -1278,9 +1256,9 @@ struct Carved3 {
     int* blockcnt;
 };
 Carved3 carve3(void* ws, int n) {
-    int* parent = static_cast<int*>(ws);
-    unsigned long long* ctrl = reinterpret_cast<unsigned long long*>(
-        (reinterpret_cast<uintptr_t>(parent + 3 * (size_t)n) + 15) & ~static_cast<uintptr_t>(15));
+    Carver c(ws);
+    int* parent = c.take<int>(3 * (size_t)n);
+    unsigned long long* ctrl = c.take<unsigned long long>(2);
     return Carved3{parent, parent + n, parent + 2 * (size_t)n, ctrl, reinterpret_cast<int*>(ctrl + 2)};
 }
 size_t ws3_bytes(int64_t nvox, bool blocks) {
@@ -1372,7 +1350,7 @@ int aide_lesion_counts3d(const long long* pred, int64_t p_s0, int64_t p_s1, int6
     if (n == 0) return 0;
     Grids gr;
     const Strided tgeo = make_strided(target, d0, d1, d2, t_s0, t_s1, t_s2, gr);
-    const Operand P{pred, (long)p_s0, (long)p_s1, (long)p_s2}, T{target, (long)t_s0, (long)t_s1, (long)t_s2};
+    const Operand P{pred, (long)p_s0, (long)p_s1, (long)p_s2, 0}, T{target, (long)t_s0, (long)t_s1, (long)t_s2, 0};
     if (int rc = lesion_side_launch(tgeo, gr, P, n, num_classes, overlap, 0, out, ws, stream)) return rc;
     const Strided pgeo = make_strided(pred, d0, d1, d2, p_s0, p_s1, p_s2, gr);
     return lesion_side_launch(pgeo, gr, T, n, num_classes, overlap, 1, out, ws, stream);
@@ -1498,7 +1476,7 @@ int aide_case_confusion(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int
     hipError_t e = hipMemsetAsync(out, 0, 4 * sizeof(long long), stream);
     if (e != hipSuccess) return (int)e;
     if (n == 0) return 0;
-    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2}, T{t, (long)t_s0, (long)t_s1, (long)t_s2};
+    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2, p_u8}, T{t, (long)t_s0, (long)t_s1, (long)t_s2, t_u8};
     const dim3 grid((unsigned)min(((long)n + 1023) / 1024, 1024L)), block(256);
     const int e1 = (int)d1, e2 = (int)d2;
     if (p_u8 && t_u8)

@@ -9,7 +9,7 @@
 // (target has c) are popcounted -- their AND is the intersection -- into wave-uniform counters.  No per-thread counters and no
 // shuffles.  The four waves of a block meet in LDS, and one 64-bit integer atomic per non-zero (class, count) and block adds
 // to the output, which a memset node zeroed.  Integer sums: the result has the same bits whatever the order of the blocks.
-#include "common.h"
+#include "volume3d.h"
 
 namespace {
 
@@ -128,19 +128,11 @@ __global__ __launch_bounds__(256) void counts_logits_kernel(const float* __restr
     block_add<C>(acc, sm, counts + (long)n * C * 3);
 }
 
-struct Operand {
-    const void* p;
-    long s0, s1, s2;
-};
-
 // two label volumes with element strides; i_c = (p == c), t_c = (t == c); a value outside [0, C) belongs to no class
 template <typename TP, typename TT>
 __global__ __launch_bounds__(256) void counts_labels_kernel(Operand P, Operand T, int d1, int d2, int n, int C,
                                                             long long* __restrict__ counts) {
     __shared__ unsigned sm[4][MAXC * 3];
-    const TP* pp = static_cast<const TP*>(P.p);
-    const TT* tp = static_cast<const TT*>(T.p);
-    const int plane = d1 * d2;
     unsigned acc[MAXC][3];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = 0u;
@@ -148,9 +140,10 @@ __global__ __launch_bounds__(256) void counts_labels_kernel(Operand P, Operand T
         const long u = base + threadIdx.x;
         long long a = -1, b = -1;
         if (u < n) {
-            const int i = (int)u, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
-            a = (long long)pp[(long)i0 * P.s0 + (long)i1 * P.s1 + (long)i2 * P.s2];
-            b = (long long)tp[(long)i0 * T.s0 + (long)i1 * T.s1 + (long)i2 * T.s2];
+            int i0, i1, i2;
+            raster_decode((int)u, d1, d2, i0, i1, i2);
+            a = P.at<TP>(P.off(i0, i1, i2));
+            b = T.at<TT>(T.off(i0, i1, i2));
         }
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
@@ -206,12 +199,6 @@ __global__ __launch_bounds__(64) void metrics_accumulate_kernel(const long long*
         acc[5 * MAXC] += N;
         acc[5 * MAXC + 1] += (long long)N * HW;
     }
-}
-
-bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
-    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
-    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
 }
 
 template <int C, int KIND, typename TT>
@@ -280,7 +267,7 @@ int aide_mc_counts_labels(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, i
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)C * 3 * sizeof(long long), stream);
     if (e != hipSuccess) return (int)e;
     if (n == 0) return 0;
-    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2}, T{t, (long)t_s0, (long)t_s1, (long)t_s2};
+    const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2, p_u8}, T{t, (long)t_s0, (long)t_s1, (long)t_s2, t_u8};
     const dim3 grid((unsigned)min(((long)n + 1023) / 1024, 1024L)), block(256);
     const int e1 = (int)d1, e2 = (int)d2;
     if (p_u8 && t_u8)

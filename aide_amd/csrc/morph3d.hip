@@ -21,9 +21,7 @@
 // No workgroup waits for another, there is no atomic at all, every word of the workspace that is read was written by an
 // earlier launch of the same call, and every thread writes only its own voxel: two calls give the same bytes.  All indices come
 // from integers.
-#include "common.h"
-
-#include <cmath>
+#include "volume3d.h"
 
 namespace {
 
@@ -33,20 +31,15 @@ constexpr unsigned char MIXED = 255;   // morph_last, merge mode: more than one 
 enum { OP_ERODE0 = 0, OP_ERODE1 = 1, OP_DILATE = 2, OP_OPEN = 3, OP_CLOSE = 4 };
 enum { TO_PLANE = 0, TO_OUT_SET = 1, TO_OUT_MERGE = 2 };
 
-struct Volume {
-    const void* p;
-    long s0, s1, s2;
-    int u8;
-};
-
 // cmap[i] = the class of voxel i: num_classes = 0: v != 0; C: v for 1 <= v < C, 0 otherwise.  out: nullptr, or a second copy
-__global__ __launch_bounds__(256) void morph_classes_kernel(Volume X, int d1, int d2, int n, int num_classes,
+__global__ __launch_bounds__(256) void morph_classes_kernel(Operand X, int d1, int d2, int n, int num_classes,
                                                             unsigned char* __restrict__ cmap, unsigned char* __restrict__ out) {
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     if (u >= (unsigned)n) return;
-    const int i = (int)u, plane = d1 * d2, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
-    const long off = (long)i0 * X.s0 + (long)i1 * X.s1 + (long)i2 * X.s2;
-    const long long v = X.u8 ? (long long)static_cast<const unsigned char*>(X.p)[off] : static_cast<const long long*>(X.p)[off];
+    const int i = (int)u;
+    int i0, i1, i2;
+    raster_decode(i, d1, d2, i0, i1, i2);
+    const long long v = X.at(X.off(i0, i1, i2));
     const unsigned char c = num_classes ? (v >= 1 && v < (long long)num_classes ? (unsigned char)v : (unsigned char)0)
                                         : (unsigned char)(v != 0);
     cmap[i] = c;
@@ -130,14 +123,6 @@ __global__ __launch_bounds__(256) void morph_last_kernel(const double* __restric
     }
 }
 
-bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
-    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
-    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
-}
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // the largest w in 0 .. d with (sp * w)^2 <= r2, in the arithmetic of the kernels (t * t + 0.0 is the rounded product, fused or not)
 int window(double r, double sp, double r2, int64_t d) {
     const double q = std::floor(r / sp);
@@ -155,6 +140,24 @@ struct Geometry {
     hipStream_t stream;
 };
 
+// f [n] fp64 | g [n] int32 | class map [n] bytes | plane between the two primitives of an opening / closing [n] bytes
+struct MorphWs {
+    double* f;
+    int* g;
+    unsigned char *cmap, *mid;
+    size_t bytes;
+};
+MorphWs morph_ws(void* ws, size_t n) {
+    Carver c(ws);
+    MorphWs w;
+    w.f = c.take<double>(n);
+    w.g = c.take<int>(n);
+    w.cmap = c.take<unsigned char>(n);
+    w.mid = c.take<unsigned char>(n);
+    w.bytes = c.used + 16;
+    return w;
+}
+
 // one primitive: candidates map == val (eq) or map != val; see morph_last_kernel for the rest
 void primitive(const Geometry& q, const unsigned char* map, int val, int eq, int faces, int invert, int mode, int cls,
                int last_class, const unsigned char* cmap, unsigned char* dst) {
@@ -171,11 +174,9 @@ void primitive(const Geometry& q, const unsigned char* map, int val, int eq, int
 
 extern "C" {
 
-// f [n] fp64 | g [n] int32 | class map [n] bytes | plane between the two primitives of an opening / closing [n] bytes
 size_t aide_morph3d_ws_bytes(int64_t nvox) {
     if (nvox < 0 || nvox > INT32_MAX) return 0;
-    const size_t n = (size_t)nvox;
-    return align16(n * sizeof(double)) + align16(n * sizeof(int)) + 2 * align16(n) + 16;
+    return morph_ws(nullptr, (size_t)nvox).bytes;
 }
 
 int aide_morph3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
@@ -185,8 +186,7 @@ int aide_morph3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, in
     if (num_classes != 0 && (num_classes < 2 || num_classes > 8)) return AIDE_ERR_ARG;
     if (op < OP_ERODE0 || op > OP_CLOSE) return AIDE_ERR_ARG;
     if (!std::isfinite(radius) || radius < 0.0) return AIDE_ERR_ARG;
-    for (int k = 0; k < 3; ++k)
-        if (!(spacing[k] > 0.0) || !std::isfinite(spacing[k])) return AIDE_ERR_ARG;
+    if (!spacing_ok(spacing)) return AIDE_ERR_ARG;
     const int n = (int)(d0 * d1 * d2);
     if (n == 0) return 0;
     if (!v || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0 || (!v_u8 && (reinterpret_cast<uintptr_t>(v) & 7) != 0))
@@ -199,19 +199,16 @@ int aide_morph3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, in
     q.w1 = window(radius, q.sp1, q.r2, d1);
     q.w2 = window(radius, q.sp2, q.r2, d2);
     q.stream = stream;
-    char* w = static_cast<char*>(ws);
-    q.f = reinterpret_cast<double*>(w);
-    w += align16((size_t)n * sizeof(double));
-    q.g = reinterpret_cast<int*>(w);
-    w += align16((size_t)n * sizeof(int));
-    unsigned char* cmap = reinterpret_cast<unsigned char*>(w);
-    unsigned char* mid = cmap + align16((size_t)n);
+    const MorphWs w = morph_ws(ws, (size_t)n);
+    q.f = w.f;
+    q.g = w.g;
+    unsigned char *cmap = w.cmap, *mid = w.mid;
     const bool merge = op == OP_DILATE || op == OP_CLOSE;
     if (!merge) {
         const hipError_t e = hipMemsetAsync(out, 0, (size_t)n, stream);
         if (e != hipSuccess) return (int)e;
     }
-    const Volume X{v, (long)s0, (long)s1, (long)s2, v_u8};
+    const Operand X{v, (long)s0, (long)s1, (long)s2, v_u8};
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (double)n * (v_u8 ? 2 : 9), morph_classes_kernel, dim3((unsigned)(((long)n + 255) / 256)),
                       dim3(256), 0, stream, X, (int)d1, (int)d2, n, num_classes, cmap, merge ? out : (unsigned char*)nullptr);
     const int classes = num_classes ? num_classes : 2;

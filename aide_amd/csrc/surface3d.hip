@@ -30,9 +30,8 @@
 // aide_edt3d (the distance transform of one volume, every voxel evaluated) runs launches 2 and 3 on one operand whose
 // candidates are its background voxels, between a launch that writes that map and edt_last, the walk along d0 with the square
 // root -- see there.
-#include "common.h"
+#include "volume3d.h"
 
-#include <cmath>
 #include <cstring>
 
 extern "C" size_t aide_surface3d_ws_bytes(int64_t nvox);
@@ -46,20 +45,14 @@ constexpr int R = 8;
 constexpr int OC = ROWS * R;       // results per chunk
 constexpr int CH = 32;             // candidates per chunk in LDS: CH * COLS doubles = 16 KiB
 
-struct Operand {
-    const void* p;
-    long s0, s1, s2;
-    int u8;
-};
-
 __device__ __forceinline__ bool fg_at(const Operand& X, long off, int cls) {
-    const long long v = X.u8 ? (long long)static_cast<const unsigned char*>(X.p)[off] : static_cast<const long long*>(X.p)[off];
+    const long long v = X.at(off);
     return cls < 0 ? v != 0 : v == (long long)cls;
 }
 
 // -> 0: background, 1: inner foreground, 2: border
 __device__ __forceinline__ int classify(const Operand& X, int i0, int i1, int i2, int d0, int d1, int d2, int cls) {
-    const long off = (long)i0 * X.s0 + (long)i1 * X.s1 + (long)i2 * X.s2;
+    const long off = X.off(i0, i1, i2);
     if (!fg_at(X, off, cls)) return 0;
     bool inner = i0 > 0 && i0 + 1 < d0 && i1 > 0 && i1 + 1 < d1 && i2 > 0 && i2 + 1 < d2;
     if (inner)
@@ -75,7 +68,9 @@ __global__ __launch_bounds__(256) void surf_border_kernel(Operand P, Operand T, 
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     int kp = 0, kt = 0;
     if (u < (unsigned)n) {
-        const int i = (int)u, plane = d1 * d2, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
+        const int i = (int)u;
+        int i0, i1, i2;
+        raster_decode(i, d1, d2, i0, i1, i2);
         kp = classify(P, i0, i1, i2, d0, d1, d2, cls);
         kt = classify(T, i0, i1, i2, d0, d1, d2, cls);
         bmap[i] = kp == 2;
@@ -116,6 +111,62 @@ struct Lines {
     double sp_in;    // !LAST: spacing of the scanned dim (d2)
 };
 
+__host__ Lines lines_d1(int d0, int d1, int d2, int n, double sp1, double sp2) {
+    return Lines{d1, d2, d2, d1 * d2, (int)((long)d0 * d2), n, sp1, sp2};
+}
+__host__ Lines lines_d0(int d0, int d1, int d2, int n, double sp0) { return Lines{d0, d1 * d2, d1 * d2, 0, d1 * d2, n, sp0, 0.0}; }
+
+// The min-plus walk of one thread's R results first .. first + R - 1 of its line: best[r] = min over the candidates j < L of
+// (sp * (first + r - j))^2 + load(j); load(j) = +inf: no candidate.  The workgroup walks the line in chunks of CH candidates
+// in LDS (live: this thread's line exists); brute force, branch-free.
+template <class Load>
+__device__ __forceinline__ void minplus_walk(int L, double sp, bool live, int first, Load load, double (&best)[R]) {
+    __shared__ double h[CH][COLS];
+    const int col = threadIdx.x & 63, row = threadIdx.x >> 6;
+    const double inf = __builtin_inf();
+#pragma unroll
+    for (int r = 0; r < R; ++r) best[r] = inf;
+    for (int j0 = 0; j0 < L; j0 += CH) {
+        __syncthreads();                         // the previous chunk is read to the end
+#pragma unroll
+        for (int k = 0; k < CH / ROWS; ++k) {
+            const int jl = k * ROWS + row, j = j0 + jl;
+            double v = inf;
+            if (live && j < L) v = load(j);
+            h[jl][col] = v;
+        }
+        __syncthreads();
+        double dd = (double)(first - j0);        // result index - candidate index, exact
+#pragma unroll 4
+        for (int jl = 0; jl < CH; ++jl) {
+            const double hv = h[jl][col];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double t = sp * (dd + (double)r);
+                best[r] = fmin(best[r], t * t + hv);
+            }
+            dd -= 1.0;
+        }
+    }
+}
+
+// {sum, max} over the 256 threads of the workgroup, folded pairwise in a fixed order; every thread gets the totals
+__device__ __forceinline__ void fold_sum_max(double& sum, double& mx) {
+    __shared__ double red[2][256];
+    red[0][threadIdx.x] = sum;
+    red[1][threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + s];
+            red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    sum = red[0][0];
+    mx = red[1][0];
+}
+
 // !LAST: f[op] from g[op].  LAST (blockIdx.y = op: 0 measures the border voxels of P against T, 1 the reverse):
 // dist[op][i] = sqrt(min) at the border voxels of operand op against f[1 - op], -1 elsewhere; part[op][blockIdx.x] = {sum, max}
 // KEYS (LAST only; aide_surface3d_scores_select): every distance is also appended to keys[op][kcnt[op]++] as its bit pattern,
@@ -127,8 +178,6 @@ __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* _
                                                            double* __restrict__ dist, double* __restrict__ part,
                                                            unsigned long long* __restrict__ keys = nullptr,
                                                            unsigned* __restrict__ kcnt = nullptr) {
-    __shared__ double h[CH][COLS];
-    __shared__ double red[2][256];
     const int op = blockIdx.y, col = threadIdx.x & 63, row = threadIdx.x >> 6;
     const long c = (long)blockIdx.x * COLS + col;
     const bool live = c < q.ncol;
@@ -140,36 +189,13 @@ __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* _
     for (int o0 = 0; o0 < q.L; o0 += OC) {
         const int first = o0 + row * R;          // this thread's results: first .. first + R - 1
         double best[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) best[r] = inf;
-        for (int j0 = 0; j0 < q.L; j0 += CH) {
-            __syncthreads();                     // the previous chunk is read to the end
-#pragma unroll
-            for (int k = 0; k < CH / ROWS; ++k) {
-                const int jl = k * ROWS + row, j = j0 + jl;
-                double v = inf;
-                if (live && j < q.L) {
-                    if (LAST) v = f[src + (size_t)j * q.stride];
-                    else {
-                        const int gi = g[src + (size_t)j * q.stride];
-                        if (gi != NONE) { const double t = q.sp_in * (double)gi; v = t * t; }
-                    }
-                }
-                h[jl][col] = v;
-            }
-            __syncthreads();
-            double dd = (double)(first - j0);    // result index - candidate index, exact
-#pragma unroll 4
-            for (int jl = 0; jl < CH; ++jl) {
-                const double hv = h[jl][col];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double t = q.sp * (dd + (double)r);
-                    best[r] = fmin(best[r], t * t + hv);
-                }
-                dd -= 1.0;
-            }
-        }
+        minplus_walk(q.L, q.sp, live, first, [&](int j) {
+            if (LAST) return f[src + (size_t)j * q.stride];
+            const int gi = g[src + (size_t)j * q.stride];
+            if (gi == NONE) return inf;
+            const double t = q.sp_in * (double)gi;
+            return t * t;
+        }, best);
         if (LAST) {
             double dk[R];
 #pragma unroll
@@ -217,21 +243,12 @@ __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* _
             }
         }
     }
-    if (LAST) {
-        red[0][threadIdx.x] = sum;
-        red[1][threadIdx.x] = mx;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) {
-                red[0][threadIdx.x] += red[0][threadIdx.x + s];
-                red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
-            }
-            __syncthreads();
-        }
+    if constexpr (LAST) {
+        fold_sum_max(sum, mx);
         if (threadIdx.x == 0) {
             double* slot = part + 2 * ((size_t)op * gridDim.x + blockIdx.x);
-            slot[0] = red[0][0];
-            slot[1] = red[1][0];
+            slot[0] = sum;
+            slot[1] = mx;
         }
     }
 }
@@ -239,7 +256,6 @@ __global__ __launch_bounds__(256) void surf_minplus_kernel(Lines q, const int* _
 // out[4], out[5] = S_PT, S_TP; out[6], out[7] = M_PT, M_TP from part[2][slots][2]: thread t adds the slots t, t + 256, ... in
 // rising order, then the 256 partial sums fold pairwise
 __global__ __launch_bounds__(256) void surf_finish_kernel(const double* __restrict__ part, int slots, double* __restrict__ out) {
-    __shared__ double red[2][256];
     for (int op = 0; op < 2; ++op) {
         double sum = 0.0, mx = 0.0;
         for (int s = threadIdx.x; s < slots; s += 256) {
@@ -248,19 +264,10 @@ __global__ __launch_bounds__(256) void surf_finish_kernel(const double* __restri
             mx = fmax(mx, slot[1]);
         }
         __syncthreads();
-        red[0][threadIdx.x] = sum;
-        red[1][threadIdx.x] = mx;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) {
-                red[0][threadIdx.x] += red[0][threadIdx.x + s];
-                red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
-            }
-            __syncthreads();
-        }
+        fold_sum_max(sum, mx);
         if (threadIdx.x == 0) {
-            out[4 + op] = red[0][0];
-            out[6 + op] = red[1][0];
+            out[4 + op] = sum;
+            out[6 + op] = mx;
         }
     }
 }
@@ -401,44 +408,22 @@ __global__ __launch_bounds__(256) void sel_choose_kernel(SelArgs a, SelState* __
 __global__ __launch_bounds__(256) void edt_bg_kernel(Operand X, int d1, int d2, int n, int cls, unsigned char* __restrict__ bmap) {
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     if (u >= (unsigned)n) return;
-    const int i = (int)u, plane = d1 * d2, i0 = i / plane, r = i - i0 * plane, i1 = r / d2, i2 = r - i1 * d2;
-    bmap[i] = !fg_at(X, (long)i0 * X.s0 + (long)i1 * X.s1 + (long)i2 * X.s2, cls);
+    int i0, i1, i2;
+    raster_decode((int)u, d1, d2, i0, i1, i2);
+    bmap[u] = !fg_at(X, X.off(i0, i1, i2), cls);
 }
 
 // the walk of surf_minplus<true> along d0 on f of the same operand, evaluated at every voxel: dist = sqrt(min).  A candidate is
 // its own nearest (min = 0, dist = 0 on the background); without any candidate every f is +inf and so is every dist.
 __global__ __launch_bounds__(256) void edt_last_kernel(Lines q, const double* __restrict__ f, double* __restrict__ dist) {
-    __shared__ double h[CH][COLS];
     const int col = threadIdx.x & 63, row = threadIdx.x >> 6;
     const long c = (long)blockIdx.x * COLS + col;
     const bool live = c < q.ncol;
     const size_t start = live ? (size_t)c : 0;
-    const double inf = __builtin_inf();
     for (int o0 = 0; o0 < q.L; o0 += OC) {
         const int first = o0 + row * R;
         double best[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) best[r] = inf;
-        for (int j0 = 0; j0 < q.L; j0 += CH) {
-            __syncthreads();                     // the previous chunk is read to the end
-#pragma unroll
-            for (int k = 0; k < CH / ROWS; ++k) {
-                const int jl = k * ROWS + row, j = j0 + jl;
-                h[jl][col] = live && j < q.L ? f[start + (size_t)j * q.stride] : inf;
-            }
-            __syncthreads();
-            double dd = (double)(first - j0);    // result index - candidate index, exact
-#pragma unroll 4
-            for (int jl = 0; jl < CH; ++jl) {
-                const double hv = h[jl][col];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double t = q.sp * (dd + (double)r);
-                    best[r] = fmin(best[r], t * t + hv);
-                }
-                dd -= 1.0;
-            }
-        }
+        minplus_walk(q.L, q.sp, live, first, [&](int j) { return f[start + (size_t)j * q.stride]; }, best);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = first + r;
@@ -447,13 +432,41 @@ __global__ __launch_bounds__(256) void edt_last_kernel(Lines q, const double* __
     }
 }
 
-bool dims_ok(int64_t d0, int64_t d1, int64_t d2) {
-    if (d0 < 0 || d1 < 0 || d2 < 0) return false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return true;
-    return d0 <= INT32_MAX && d1 <= INT32_MAX && d2 <= INT32_MAX && d1 * d2 <= INT32_MAX && d0 * (d1 * d2) <= INT32_MAX;
+// f [2][n] fp64 | g [2][n] int32 | bmap [2][n] bytes | slots [2][ceil(n / 64)][2] fp64 (d1 * d2 <= n: as many as any shape needs)
+struct SurfaceWs {
+    double* f;
+    int* g;
+    unsigned char* bmap;
+    double* part;
+    size_t bytes;
+};
+SurfaceWs surface_ws(void* ws, size_t n) {
+    Carver c(ws);
+    SurfaceWs w;
+    w.f = c.take<double>(2 * n);
+    w.g = c.take<int>(2 * n);
+    w.bmap = c.take<unsigned char>(2 * n);
+    w.part = c.take<double>(4 * ((n + COLS - 1) / COLS));
+    w.bytes = c.used + 16;
+    return w;
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+// f [n] fp64 | g [n] int32 | candidate map [n] bytes
+struct EdtWs {
+    double* f;
+    int* g;
+    unsigned char* bmap;
+    size_t bytes;
+};
+EdtWs edt_ws(void* ws, size_t n) {
+    Carver c(ws);
+    EdtWs w;
+    w.f = c.take<double>(n);
+    w.g = c.take<int>(n);
+    w.bmap = c.take<unsigned char>(n);
+    w.bytes = c.used + 16;
+    return w;
+}
 
 constexpr int SEL_WORDS = 52;      // out of aide_surface3d_scores_select, in words of 8 bytes
 constexpr size_t SEL_CTRL_BYTES = 16 + SEL_T * sizeof(SelState) + SEL_T * 256 * sizeof(unsigned);
@@ -472,8 +485,8 @@ int surface_run(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s
                 const SelArgs* sel, void* out, double* dist, void* ws, hipStream_t stream) {
     if (!dims_ok(d0, d1, d2) || !p || !t || !out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIDE_ERR_ARG;
     if ((p_u8 != 0 && p_u8 != 1) || (t_u8 != 0 && t_u8 != 1)) return AIDE_ERR_ARG;
-    if (!(sp0 > 0.0 && sp1 > 0.0 && sp2 > 0.0) || !std::isfinite(sp0) || !std::isfinite(sp1) || !std::isfinite(sp2))
-        return AIDE_ERR_ARG;
+    const double sp[3] = {sp0, sp1, sp2};
+    if (!spacing_ok(sp)) return AIDE_ERR_ARG;
     const int n = (int)(d0 * d1 * d2);
     const int plane = (int)(d1 * d2);
     const long cols1 = (long)d0 * d2, cols0 = plane;                        // lines along d1, along d0
@@ -481,22 +494,15 @@ int surface_run(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s
     hipError_t e = hipMemsetAsync(out, 0, (sel ? SEL_WORDS : 8) * sizeof(double), stream);
     if (e != hipSuccess) return (int)e;
     if (n == 0) return 0;
-    char* w = static_cast<char*>(ws);
-    double* f = reinterpret_cast<double*>(w);
-    w += align16(2 * (size_t)n * sizeof(double));
-    int* g = reinterpret_cast<int*>(w);
-    w += align16(2 * (size_t)n * sizeof(int));
-    unsigned char* bmap = reinterpret_cast<unsigned char*>(w);
-    w += align16(2 * (size_t)n);
-    double* part = reinterpret_cast<double*>(w);
+    const SurfaceWs w = surface_ws(ws, (size_t)n);
+    double* f = w.f;
+    int* g = w.g;
+    unsigned char* bmap = w.bmap;
+    double* part = w.part;
     const Operand P{p, (long)p_s0, (long)p_s1, (long)p_s2, p_u8}, T{t, (long)t_s0, (long)t_s1, (long)t_s2, t_u8};
     const unsigned nb = (unsigned)(((long)n + 255) / 256);
     const int lines = (int)(d0 * d1);
-    Lines a1, a0;
-    a1.L = (int)d1; a1.stride = (int)d2; a1.inner = (int)d2; a1.outer = plane; a1.ncol = (int)cols1; a1.n = n;
-    a1.sp = sp1; a1.sp_in = sp2;
-    a0.L = (int)d0; a0.stride = plane; a0.inner = plane; a0.outer = 0; a0.ncol = (int)cols0; a0.n = n;
-    a0.sp = sp0; a0.sp_in = 0.0;
+    const Lines a1 = lines_d1((int)d0, (int)d1, (int)d2, n, sp1, sp2), a0 = lines_d0((int)d0, (int)d1, (int)d2, n, sp0);
     const dim3 block(256);
     unsigned long long* keys = nullptr;
     unsigned* kcnt = nullptr;
@@ -515,7 +521,7 @@ int surface_run(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s
                           stream, a0, (const int*)g, f, (const unsigned char*)bmap, dist, part, (unsigned long long*)nullptr,
                           (unsigned*)nullptr);
     } else {
-        char* w2 = static_cast<char*>(ws) + aide_surface3d_ws_bytes(n);
+        char* w2 = static_cast<char*>(ws) + w.bytes;
         keys = reinterpret_cast<unsigned long long*>(w2);
         w2 += 2 * (size_t)n * sizeof(unsigned long long);
         kcnt = reinterpret_cast<unsigned*>(w2);
@@ -546,12 +552,9 @@ int surface_run(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s
 
 extern "C" {
 
-// f [2][n] fp64 | g [2][n] int32 | bmap [2][n] bytes | slots [2][ceil(n / 64)][2] fp64 (d1 * d2 <= n: as many as any shape needs)
 size_t aide_surface3d_ws_bytes(int64_t nvox) {
     if (nvox < 0 || nvox > INT32_MAX) return 0;
-    const size_t n = (size_t)nvox;
-    const size_t slots = (n + COLS - 1) / COLS;
-    return align16(2 * n * sizeof(double)) + align16(2 * n * sizeof(int)) + align16(2 * n) + 4 * slots * sizeof(double) + 16;
+    return surface_ws(nullptr, (size_t)nvox).bytes;
 }
 
 int aide_surface3d_scores(const void* p, int p_u8, int64_t p_s0, int64_t p_s1, int64_t p_s2, const void* t, int t_u8,
@@ -592,19 +595,15 @@ int aide_surface3d_scores_select(const void* p, int p_u8, int64_t p_s0, int64_t 
                        stream);
 }
 
-// g [n] int32 | f [n] fp64 | candidate map [n] bytes
 size_t aide_edt3d_ws_bytes(int64_t nvox) {
     if (nvox < 0 || nvox > INT32_MAX) return 0;
-    const size_t n = (size_t)nvox;
-    return align16(n * sizeof(double)) + align16(n * sizeof(int)) + align16(n) + 16;
+    return edt_ws(nullptr, (size_t)nvox).bytes;
 }
 
 int aide_edt3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2, int cls,
                const double* spacing, double* dist, void* ws, hipStream_t stream) {
     if (!dims_ok(d0, d1, d2) || !spacing || (v_u8 != 0 && v_u8 != 1)) return AIDE_ERR_ARG;
-    const double sp0 = spacing[0], sp1 = spacing[1], sp2 = spacing[2];
-    if (!(sp0 > 0.0 && sp1 > 0.0 && sp2 > 0.0) || !std::isfinite(sp0) || !std::isfinite(sp1) || !std::isfinite(sp2))
-        return AIDE_ERR_ARG;
+    if (!spacing_ok(spacing)) return AIDE_ERR_ARG;
     const int n = (int)(d0 * d1 * d2);
     if (n == 0) return 0;
     if (!v || !dist || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0 || (reinterpret_cast<uintptr_t>(dist) & 7) != 0 ||
@@ -612,28 +611,20 @@ int aide_edt3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int6
         return AIDE_ERR_ARG;
     const int plane = (int)(d1 * d2), lines = (int)(d0 * d1);
     const long cols1 = (long)d0 * d2;
-    char* w = static_cast<char*>(ws);
-    double* f = reinterpret_cast<double*>(w);
-    w += align16((size_t)n * sizeof(double));
-    int* g = reinterpret_cast<int*>(w);
-    w += align16((size_t)n * sizeof(int));
-    unsigned char* bmap = reinterpret_cast<unsigned char*>(w);
+    const EdtWs w = edt_ws(ws, (size_t)n);
     const Operand X{v, (long)s0, (long)s1, (long)s2, v_u8};
-    Lines a1, a0;
-    a1.L = (int)d1; a1.stride = (int)d2; a1.inner = (int)d2; a1.outer = plane; a1.ncol = (int)cols1; a1.n = n;
-    a1.sp = sp1; a1.sp_in = sp2;
-    a0.L = (int)d0; a0.stride = plane; a0.inner = plane; a0.outer = 0; a0.ncol = plane; a0.n = n;
-    a0.sp = sp0; a0.sp_in = 0.0;
+    const Lines a1 = lines_d1((int)d0, (int)d1, (int)d2, n, spacing[1], spacing[2]),
+                a0 = lines_d0((int)d0, (int)d1, (int)d2, n, spacing[0]);
     const dim3 block(256);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, (double)n * (v_u8 ? 2 : 9), edt_bg_kernel, dim3((unsigned)(((long)n + 255) / 256)), block, 0,
-                      stream, X, (int)d1, (int)d2, n, cls, bmap);
+                      stream, X, (int)d1, (int)d2, n, cls, w.bmap);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 5.0 * n, surf_scan2_kernel, dim3((unsigned)((lines + 255) / 256), 1), block, 0, stream,
-                      (const unsigned char*)bmap, lines, (int)d2, n, g);
+                      (const unsigned char*)w.bmap, lines, (int)d2, n, w.g);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 12.0 * n, surf_minplus_kernel<false>, dim3((unsigned)((cols1 + COLS - 1) / COLS), 1), block,
-                      0, stream, a1, (const int*)g, f, (const unsigned char*)nullptr, (double*)nullptr, (double*)nullptr,
+                      0, stream, a1, (const int*)w.g, w.f, (const unsigned char*)nullptr, (double*)nullptr, (double*)nullptr,
                       (unsigned long long*)nullptr, (unsigned*)nullptr);
     AIDE_LAUNCH_TIMED(AIDE_KT_OTHER, 16.0 * n, edt_last_kernel, dim3((unsigned)((plane + COLS - 1) / COLS)), block, 0, stream, a0,
-                      (const double*)f, dist);
+                      (const double*)w.f, dist);
     return aide_launch_status();
 }
 

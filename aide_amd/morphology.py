@@ -38,20 +38,9 @@ import torch
 
 from ._lib import lib, check
 from .ops import ptr, stream_ptr
+from .volumes import classes as _classes, device_volume, host_volume, spacing as _spacing, u8, workspace
 
 OPS = {'erode0': 0, 'erode1': 1, 'dilate': 2, 'open': 3, 'close': 4}
-_MAX_VOX = 2 ** 31 - 1
-_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8, torch.bool)
-
-
-def _spacing(spacing, what):
-    try:
-        sp = tuple(float(s) for s in spacing)
-    except TypeError:
-        sp = ()
-    if len(sp) != 3 or not all(math.isfinite(s) and s > 0.0 for s in sp):
-        raise ValueError('%s: spacing %r, three finite positive numbers are expected' % (what, spacing))
-    return sp
 
 
 def _radius(radius, what):
@@ -59,14 +48,6 @@ def _radius(radius, what):
             or not math.isfinite(radius) or radius < 0:
         raise ValueError('%s: radius %r, a finite number >= 0 is expected' % (what, radius))
     return float(radius)
-
-
-def _classes(num_classes, what):
-    if num_classes is None:
-        return None
-    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 2 <= num_classes <= 8:
-        raise ValueError('%s: num_classes %r, None or 2 .. 8 are supported' % (what, num_classes))
-    return int(num_classes)
 
 
 def _window(r, sp, limit=None):
@@ -91,28 +72,6 @@ def ball(radius, spacing=(1.0, 1.0, 1.0)):
     """The structuring element B(radius): a boolean array of shape (2 W0 + 1, 2 W1 + 1, 2 W2 + 1), W_k = floor(radius / sp_k),
     centred on offset 0, True where q(o) <= radius * radius."""
     return _ball(_radius(radius, 'ball'), _spacing(spacing, 'ball'))
-
-
-def _host_volume(volume, what):
-    if isinstance(volume, torch.Tensor):
-        volume = volume.detach().numpy()
-    volume = np.asarray(volume)
-    if volume.ndim != 3:
-        raise RuntimeError('%s: a 3-D volume is expected, got %d dims' % (what, volume.ndim))
-    if volume.dtype != np.bool_ and not np.issubdtype(volume.dtype, np.integer):
-        raise RuntimeError('%s: integer labels expected, got %s' % (what, volume.dtype))
-    return volume
-
-
-def _device_volume(volume, what):
-    if volume.dim() != 3:
-        raise RuntimeError('%s: a 3-D volume is expected, got %d dims' % (what, volume.dim()))
-    if volume.dtype not in _INT_DTYPES:
-        raise RuntimeError('%s: integer labels expected, got %s' % (what, volume.dtype))
-    if volume.numel() > _MAX_VOX:
-        raise RuntimeError('%s: %d voxels, at most 2^31 - 1' % (what, volume.numel()))
-    v = volume.detach()
-    return v if v.dtype in (torch.int64, torch.uint8) else v.to(torch.int64)
 
 
 def _plane_host(x, op, b):
@@ -152,15 +111,15 @@ def _morph_host(vol, op, r, sp, c):
 def _morph(volume, op, radius, spacing, num_classes, what):
     r, sp, c = _radius(radius, what), _spacing(spacing, what), _classes(num_classes, what)
     if isinstance(volume, torch.Tensor) and volume.is_cuda:
-        v = _device_volume(volume, what)
+        v = device_volume(volume, what, keep_uint8=True)
         out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
         if v.numel() == 0:
             return out
-        ws = torch.empty(lib.aide_morph3d_ws_bytes(v.numel()), device=v.device, dtype=torch.uint8)
-        check(lib.aide_morph3d(ptr(v), int(v.dtype == torch.uint8), *v.shape, *v.stride(), c or 0, OPS[op], r,
+        ws = workspace(lib.aide_morph3d_ws_bytes, v)
+        check(lib.aide_morph3d(ptr(v), u8(v), *v.shape, *v.stride(), c or 0, OPS[op], r,
                                (ctypes.c_double * 3)(*sp), ptr(out), ptr(ws), stream_ptr()), 'morph3d')
         return out
-    return _morph_host(_host_volume(volume, what), op, r, sp, c)
+    return _morph_host(host_volume(volume, what), op, r, sp, c)
 
 
 def erode(volume, radius, spacing=(1.0, 1.0, 1.0), num_classes=None, outside=0):
@@ -198,15 +157,15 @@ def distance_transform(volume, spacing=(1.0, 1.0, 1.0), cls=None):
     if cls is not None and (isinstance(cls, bool) or not isinstance(cls, (int, np.integer)) or not 0 <= cls < 2 ** 31):
         raise ValueError('distance_transform: cls %r, None or a class value >= 0 is expected' % (cls,))
     if isinstance(volume, torch.Tensor) and volume.is_cuda:
-        v = _device_volume(volume, 'distance_transform')
+        v = device_volume(volume, 'distance_transform', keep_uint8=True)
         dist = torch.empty(v.shape, device=v.device, dtype=torch.float64)
         if v.numel() == 0:
             return dist
-        ws = torch.empty(lib.aide_edt3d_ws_bytes(v.numel()), device=v.device, dtype=torch.uint8)
-        check(lib.aide_edt3d(ptr(v), int(v.dtype == torch.uint8), *v.shape, *v.stride(), -1 if cls is None else int(cls),
+        ws = workspace(lib.aide_edt3d_ws_bytes, v)
+        check(lib.aide_edt3d(ptr(v), u8(v), *v.shape, *v.stride(), -1 if cls is None else int(cls),
                              (ctypes.c_double * 3)(*sp), ptr(dist), ptr(ws), stream_ptr()), 'edt3d')
         return dist
-    vol = _host_volume(volume, 'distance_transform')
+    vol = host_volume(volume, 'distance_transform')
     fg = (vol != 0) if cls is None else (vol == cls)
     if fg.size == 0:
         return np.zeros(fg.shape, np.float64)

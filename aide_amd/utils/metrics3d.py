@@ -32,7 +32,8 @@ import torch
 
 from .._lib import lib, check
 from ..ops import ptr, stream_ptr
-from ..inference import Dice3d_fn, case_scores, _confusion_args, _as3d  # noqa: F401
+from ..inference import Dice3d_fn, case_scores  # noqa: F401
+from ..volumes import classes, device_pair, spacing as _spacing, u8, workspace
 
 
 def IoU3d_fn(inputs, targets):
@@ -46,23 +47,10 @@ def TP_TN_FP_FN3d(inputs, targets):
     return s['TP'], s['TN'], s['FP'], s['FN']
 
 
-def _spacing(spacing):
-    try:
-        sp = tuple(float(v) for v in spacing)
-    except TypeError:
-        raise ValueError('spacing: three positive numbers expected, got %r' % (spacing,))
-    if len(sp) != 3 or not all(math.isfinite(v) and v > 0.0 for v in sp):
-        raise ValueError('spacing: three positive finite numbers expected, got %r' % (spacing,))
-    return sp
-
-
 def _classes(num_classes):
     if num_classes is None:
         return [-1]
-    c = int(num_classes)
-    if not 2 <= c <= 8:
-        raise RuntimeError('surface_scores: num_classes %d, 2 .. 8 are supported' % c)
-    return list(range(1, c))
+    return list(range(1, classes(num_classes, 'surface_scores', strict=False)))
 
 
 def _raw_host(p, t, sp, cls, distances):
@@ -143,31 +131,28 @@ def _select_host(maps, n_p, n_t, qs, taus):
     return within, lo, x_lo, x_hi
 
 
-def _raw_device(pred, target, sp, classes, distances, qs=(), taus=()):
-    """-> int64 [K,4], float64 [K,4] (numpy) and the distance tensor [K,2,d0,d1,d2] or None, for the K entries of `classes`:
+def _raw_device(pred, target, sp, cls_values, distances, qs=(), taus=()):
+    """-> int64 [K,4], float64 [K,4] (numpy) and the distance tensor [K,2,d0,d1,d2] or None, for the K entries of `cls_values`:
     K calls enqueued back to back on one workspace, one copy of K * 8 words.  With percentiles or tolerances the calls are
     aide_surface3d_scores_select's, the copy is K * 52 words, and a fourth value carries (within [K,4,2], lo [K,3,4], x_lo,
     x_hi [K,3,4]); None otherwise."""
-    _confusion_args(pred, target)
-    p, t = _as3d(pred), _as3d(target)
-    k, n = len(classes), p.numel()
+    p, t = device_pair(pred, target, 'surface_scores')
+    k, n = len(cls_values), p.numel()
     select = bool(qs or taus)
     out = torch.zeros(k, 52 if select else 8, device=p.device, dtype=torch.int64)
     dist = torch.full((k, 2) + tuple(p.shape), -1.0, device=p.device, dtype=torch.float64) if distances else None
     if n and select:
         import ctypes
         cq, ct = (ctypes.c_double * 4)(*qs), (ctypes.c_double * 4)(*taus)
-        ws = torch.empty(lib.aide_surface3d_select_ws_bytes(n), device=p.device, dtype=torch.uint8)
-        for i, c in enumerate(classes):
-            check(lib.aide_surface3d_scores_select(ptr(p), int(p.dtype == torch.uint8), *p.stride(), ptr(t),
-                                                   int(t.dtype == torch.uint8), *t.stride(), *p.shape, sp[0], sp[1], sp[2], c,
-                                                   cq, len(qs), ct, len(taus), ptr(out[i]), ptr(dist[i]) if distances else None,
+        ws = workspace(lib.aide_surface3d_select_ws_bytes, p)
+        for i, c in enumerate(cls_values):
+            check(lib.aide_surface3d_scores_select(ptr(p), u8(p), *p.stride(), ptr(t), u8(t), *t.stride(), *p.shape, *sp, c, cq,
+                                                   len(qs), ct, len(taus), ptr(out[i]), ptr(dist[i]) if distances else None,
                                                    ptr(ws), stream_ptr()), 'surface3d_scores_select')
     elif n:
-        ws = torch.empty(lib.aide_surface3d_ws_bytes(n), device=p.device, dtype=torch.uint8)
-        for i, c in enumerate(classes):
-            check(lib.aide_surface3d_scores(ptr(p), int(p.dtype == torch.uint8), *p.stride(), ptr(t), int(t.dtype == torch.uint8),
-                                            *t.stride(), *p.shape, sp[0], sp[1], sp[2], c, ptr(out[i]),
+        ws = workspace(lib.aide_surface3d_ws_bytes, p)
+        for i, c in enumerate(cls_values):
+            check(lib.aide_surface3d_scores(ptr(p), u8(p), *p.stride(), ptr(t), u8(t), *t.stride(), *p.shape, *sp, c, ptr(out[i]),
                                             ptr(dist[i]) if distances else None, ptr(ws), stream_ptr()), 'surface3d_scores')
     words = out.cpu().numpy()
     sel = None
@@ -233,8 +218,8 @@ def surface_scores(pred, target, spacing, num_classes=None, distances=False, per
     HIP tensors (integer dtypes, any strides: a [S,H,W] tensor passed as .permute(1, 2, 0) works): five launches per class,
     enqueued back to back, one copy of [C][8] words, the divisions on the host in float64; the distance maps stay on the device.
     numpy arrays and CPU tensors: scipy (binary_erosion, distance_transform_edt), numpy maps."""
-    sp = _spacing(spacing)
-    classes = _classes(num_classes)
+    sp = _spacing(spacing, 'surface_scores')
+    cls_values = _classes(num_classes)
     qs = _numbers(percentiles, 'percentiles', lambda v: 0.0 <= v <= 100.0)
     taus = _numbers(tolerances, 'tolerances', lambda v: v >= 0.0)
     select = bool(qs or taus)
@@ -244,7 +229,7 @@ def surface_scores(pred, target, spacing, num_classes=None, distances=False, per
         target = torch.as_tensor(target, device=dev[0].device)
         if pred.dim() != 3:
             raise RuntimeError('surface_scores: 3-D volumes expected, got %d dims' % pred.dim())
-        ints, flts, dist, sel = _raw_device(pred, target, sp, classes, distances, qs, taus)
+        ints, flts, dist, sel = _raw_device(pred, target, sp, cls_values, distances, qs, taus)
         maps = (dist[:, 0], dist[:, 1]) if distances else None
     else:
         p, t = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in (pred, target))
@@ -252,7 +237,7 @@ def surface_scores(pred, target, spacing, num_classes=None, distances=False, per
             raise RuntimeError('surface_scores: shape mismatch %s vs %s' % (p.shape, t.shape))
         if p.ndim != 3:
             raise RuntimeError('surface_scores: 3-D volumes expected, got %d dims' % p.ndim)
-        raw = [_raw_host(p, t, sp, c, distances or select) for c in classes]
+        raw = [_raw_host(p, t, sp, c, distances or select) for c in cls_values]
         ints = np.array([r[0] for r in raw], np.int64).reshape(-1, 4)
         flts = np.array([r[1] for r in raw], np.float64).reshape(-1, 4)
         maps = tuple(np.stack([r[2][k] for r in raw]) for k in range(2)) if distances else None

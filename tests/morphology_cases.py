@@ -23,7 +23,7 @@ import math
 
 import numpy as np
 
-from surface_cases import REL  # noqa: F401  (the ulp bound of the distance arithmetic)
+from surface_cases import REL, EDGE_SHAPES  # noqa: F401  (the ulp bound of the distance arithmetic; the edges of its walk)
 
 UNIT = (1.0, 1.0, 1.0)
 SPACING = (0.9, 1.3, 2.5)

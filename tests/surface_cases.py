@@ -15,6 +15,14 @@ import numpy as np
 REL = 2.0 ** -49
 SPACINGS = ((1.0, 1.0, 1.0), (0.7, 0.7, 5.5), (1.37, 1.37, 7.7))
 SMALL_SHAPES = ((5, 37, 19), (1, 7, 1), (33, 1, 40), (17, 31, 16))
+# The edges of the min-plus walk (csrc/surface3d.hip), which the surface scores and the distance transform share: it takes the
+# lines along d1 and then along d0 in chunks of 32 candidates and 32 results, 64 neighbouring lines (columns) per workgroup.
+# Line lengths 1, 31, 32, 33, 65 on both axes: below, at and past a chunk, and a second chunk; column counts 1, 63, 64, 65 in
+# both passes (d0 * d2 along d1, d1 * d2 along d0): a partial workgroup, a full one, and a second one.
+EDGE_SHAPES = ((33, 1, 1), (65, 1, 2), (1, 33, 1), (2, 65, 1), (31, 9, 7), (32, 1, 64), (1, 1, 65), (9, 31, 7), (64, 32, 1))
+for _axis in (0, 1):                              # a condition on the chosen inputs
+    assert {1, 31, 32, 33, 65} <= {s[_axis] for s in EDGE_SHAPES}
+    assert {1, 63, 64, 65} <= {s[1 - _axis] * s[2] for s in EDGE_SHAPES}
 
 
 def _fg(x, cls):

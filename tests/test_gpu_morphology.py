@@ -107,6 +107,30 @@ def test_distance_transform(dev):
     assert distance_transform(torch.zeros(0, 4, 4, dtype=torch.int64, device=dev)).shape == (0, 4, 4)
 
 
+@pytest.mark.parametrize('shape', mc.EDGE_SHAPES, ids=['%dx%dx%d' % s for s in mc.EDGE_SHAPES])
+def test_distance_transform_chunk_and_workgroup_edges(dev, shape):
+    """line lengths around the chunk of 32 and column counts around the workgroup of 64 of the walk the distance transform shares
+    with the surface scores (surface_cases.EDGE_SHAPES) against the host path (scipy): int64 and uint8, a permuted view, every
+    voxel a candidate (all background) and no candidate at all (all foreground: +inf)"""
+    from aide_amd.morphology import distance_transform
+    for density in (0.6, 0.97):
+        vol = (np.random.RandomState(shape[0] + 3 * shape[1] + int(100 * density)).rand(*shape) < density).astype(np.int64)
+        vol.flat[0] = 0                                                  # at least one background voxel
+        unit, mm = distance_transform(vol), distance_transform(vol, mc.SPACING)
+        assert np.array_equal(unit == 0.0, vol == 0) and np.isfinite(mm).all()
+        view = torch.from_numpy(np.ascontiguousarray(vol.transpose(2, 0, 1))).to(dev).permute(1, 2, 0)   # [S,H,W] storage
+        for t in (torch.from_numpy(vol).to(dev), torch.from_numpy(vol.astype(np.uint8)).to(dev), view):
+            assert tuple(t.shape) == shape
+            assert np.array_equal(distance_transform(t).cpu().numpy(), unit), (shape, density, t.dtype)   # integers: bit-equal
+            got = distance_transform(t, mc.SPACING).cpu().numpy()
+            assert np.all(np.abs(got - mm) <= mc.REL * mm), (shape, density, t.dtype)
+            assert np.array_equal(got == 0.0, vol == 0)
+    for dtype in (torch.int64, torch.uint8):
+        full = torch.ones(shape, dtype=dtype, device=dev)
+        assert torch.isposinf(distance_transform(full, mc.SPACING)).all() and np.isposinf(distance_transform(full.cpu().numpy())).all()
+        assert not distance_transform(full * 0, mc.SPACING).any()
+
+
 def test_layouts_and_types(dev):
     """int64 and uint8, contiguous and as the permute(1, 2, 0) view of [S,H,W] that predict_case produces: the same bytes"""
     from aide_amd.morphology import distance_transform

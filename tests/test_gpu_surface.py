@@ -66,6 +66,28 @@ def test_lines_longer_than_a_chunk(dev, shape):
     assert ref['n_P'] == ref['n_T'] == 1
 
 
+@pytest.mark.parametrize('shape', sc.EDGE_SHAPES, ids=['%dx%dx%d' % s for s in sc.EDGE_SHAPES])
+def test_chunk_and_workgroup_edges(dev, shape):
+    """line lengths around the chunk of 32 and column counts around the workgroup of 64 (surface_cases.EDGE_SHAPES), int64 and
+    uint8, a permuted view, a volume that is all border and one without any"""
+    for density in (0.3, 0.9):
+        p, t = sc.random_pair(shape, density, seed=shape[0] + 7 * shape[1] + int(10 * density))
+        _check(p, t, dev, what=('edges', density))
+        _check(p.astype(np.uint8), t, dev, spacings=((5.5, 0.7, 0.7),), what=('edges uint8', density))
+        view = torch.from_numpy(np.ascontiguousarray(p.transpose(2, 0, 1))).to(dev).permute(1, 2, 0)     # [S,H,W] storage
+        assert tuple(view.shape) == shape
+        _check(view, torch.from_numpy(t).to(dev), dev, spacings=((0.7, 0.7, 5.5),), what=('edges permuted', density))
+    full, zero = np.ones(shape, np.int64), np.zeros(shape, np.int64)
+    part, _ = sc.random_pair(shape, 0.5, seed=shape[2])
+    ref = _check(full, full, dev, what='edges full / full')
+    assert min(shape) > 2 or ref['n_P'] == full.size      # a dim of 1 or 2: every voxel is a border voxel, every f is 0
+    _check(full, part, dev, what='edges full / random')
+    for a, b in ((zero, part), (part, zero)):             # one side without a border voxel: every f is +inf
+        words, dist = _raw_call(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), (0.7, 0.7, 5.5))
+        sc.check_raw(_as_raw(words, dist), sc.reference(a, b, (0.7, 0.7, 5.5)), (0.7, 0.7, 5.5), 'edges empty')
+        assert np.all(dist == -1.0) and np.all(words[4:] == 0)
+
+
 def test_ellipsoid_pairs(dev):
     for shape, spacings in (((64, 64, 33), ALL_SPACINGS), ((256, 256, 33), ((1.37, 1.37, 7.7),))):
         p, t = sc.ellipsoid_pair(shape)
