@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'libaide_hip.so')
 SOURCES = ['conv3x3.hip', 'conv3x3_winograd.hip', 'conv3x3_wino4.hip', 'conv3x3_wgrad.hip', 'conv3x3_wgrad4.hip', 'conv3x3_wgrad_stem.hip', 'conv3x3_bf16.hip', 'bn.hip', 'spatial.hip', 'loss.hip', 'coteach_ext.hip', 'head_adam.hip',
-           'convt.hip', 'attention.hip', 'ktimer.hip', 'eval3d.hip', 'augment.hip', 'labelbank.hip', 'metrics_mc.hip', 'surface3d.hip', 'ensemble.hip', 'window.hip', 'morph3d.hip']
+           'convt.hip', 'attention.hip', 'ktimer.hip', 'eval3d.hip', 'augment.hip', 'labelbank.hip', 'metrics_mc.hip', 'surface3d.hip', 'ensemble.hip', 'window.hip', 'morph3d.hip', 'resample3d.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast']
 
 

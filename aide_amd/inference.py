@@ -21,10 +21,11 @@ from .ensemble import (VIEW_SETS, view_codes, view_apply_host, view_invert_host,
 from .window import (window_grid, window_weights, window_stack, window_blend, window_blend_host,  # noqa: F401
                      predict_windows)
 from .morphology import ball, erode, dilate, open_, close, distance_transform  # noqa: F401
+from .resample import axis_table, resampled_shape, resample_image, resample_labels, resample_probs  # noqa: F401
 from .postprocess import (MAX_TOP_K, MAX_BLOBS, PROPS_COLUMNS, LESION_COLUMNS, keep_largest_connected_components,  # noqa: F401
                           keep_largest_per_class, keep_components, fill_holes, label_components, region_table, lesion_counts,
                           lesion_scores, keep_largest_batched, _overlap, _starts)
-from .volumes import classes, device_pair, u8, volume_args
+from .volumes import classes, device_pair, spacing as _spacing, u8, volume_args
 
 
 def label_map(logits):
@@ -90,6 +91,24 @@ def _window_kw(kw):
 _UNSET = object()
 
 
+def _target_grid(modal_inputs, spacing, target, windowed):
+    """(H', W') of the slices at the in-plane spacing `target`, or None when that is the grid they are on"""
+    try:
+        t = tuple(float(v) for v in target)
+    except TypeError:
+        t = ()
+    if len(t) != 2:
+        raise ValueError('predict_case: target_spacing %r, two finite positive numbers (t_h, t_w) are expected' % (target,))
+    s, _, h, w = modal_inputs[0].shape
+    sp = _spacing(spacing, 'predict_case')
+    (hn, wn, _), _ = resampled_shape((h, w, max(s, 1)), sp, t + sp[2:])
+    if (hn, wn) == (h, w):
+        return None
+    if not windowed and (hn % 16 or wn % 16):
+        raise ValueError('predict_case: the slices are %d x %d at target_spacing, not multiples of 16: pass window=' % (hn, wn))
+    return hn, wn
+
+
 def predict_case(net, *modal_inputs, **kw):
     """The reference's `generatedtarget`: numpy int64 [H,W,S] (slices stacked on the last axis, :267).
     keep_largest=True: its largest connected component (:268), uint8, filtered on the device before anything leaves it.
@@ -108,7 +127,13 @@ def predict_case(net, *modal_inputs, **kw):
     opening=r / closing=r (millimetres, with spacing=(sp_h, sp_w, sp_s), default 1 mm cubes; aide_amd/morphology.py): `open_`
     with the ball of radius r on the labels before the filter, `close` after fill_holes; both per class exactly when the filter
     is (keep_largest='per_class', or num_classes with no filter), binary otherwise.  spacing without either: TypeError.  With
-    both at their defaults every call takes the path it took before."""
+    both at their defaults every call takes the path it took before.
+    target_spacing=(t_h, t_w) (with spacing=; TypeError without it; aide_amd/resample.py): the in-plane spacing the network was
+    trained at.  Every modal input is resampled per slice and channel to (H', W') = `resampled_shape` (order 1), the mean
+    probabilities are predicted on that grid (views / lists of networks / window= compose; without window= an (H', W') that is
+    not a multiple of 16 is a ValueError) and brought back to (S, H, W) with `resample_probs`: the labels, and with probs=True
+    the probabilities, are the resampled ones, and opening, the filters, fill_holes and closing run on the native grid.
+    (H', W') == (H, W) skips both resamples; target_spacing=None (the default): every call takes the path it took before."""
     keep_largest = kw.pop('keep_largest', False)
     want_probs = kw.pop('probs', False)
     num_classes = kw.pop('num_classes', None)
@@ -120,8 +145,11 @@ def predict_case(net, *modal_inputs, **kw):
     opening = kw.pop('opening', None)
     closing = kw.pop('closing', None)
     spacing = kw.pop('spacing', None)
+    target = kw.pop('target_spacing', None)
     morph = opening is not None or closing is not None
-    if spacing is not None and not morph:
+    if target is not None and spacing is None:
+        raise TypeError('predict_case: target_spacing needs spacing=(sp_h, sp_w, sp_s)')
+    if spacing is not None and not morph and target is None:
         raise TypeError('predict_case: spacing goes with opening / closing')
     per_class = isinstance(keep_largest, str)
     if per_class:
@@ -140,7 +168,14 @@ def predict_case(net, *modal_inputs, **kw):
     if slice_axis is not None and not fill:
         raise TypeError('predict_case: slice_axis goes with fill_holes=True')
     pr = None
-    if want_probs:
+    native = None if target is None else _target_grid(modal_inputs, spacing, target, kw.get('window') is not None)
+    if native is not None:
+        first = net[0] if isinstance(net, (list, tuple)) else net
+        dev = next(first.parameters()).device
+        s, _, h, w = modal_inputs[0].shape
+        modal_inputs = tuple(resample_image(m.to(dev).reshape(-1, 1, h, w), (1,) + native).reshape(tuple(m.shape[:2]) + native)
+                             for m in modal_inputs)
+    if want_probs or native is not None:
         views = kw.pop('views', None)
         batch_size = kw.pop('batch_size', 16)
         win = _window_kw(kw)
@@ -150,6 +185,9 @@ def predict_case(net, *modal_inputs, **kw):
             vol, pr = predict_windows(net, modal_inputs, views=views, batch_size=batch_size, probs=True, **win)
         else:
             vol, pr = predict_ensemble(net, modal_inputs, (0,) if views is None else views, batch_size=batch_size, probs=True)
+        if native is not None:
+            vol = resample_probs(pr, (s, h, w), probs_out=want_probs)
+            vol, pr = vol if want_probs else (vol, None)
         vol = vol.permute(1, 2, 0)
     else:
         vol = predict_labels(net, *modal_inputs, **kw).permute(1, 2, 0)

@@ -694,6 +694,47 @@ int aide_morph3d(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, in
                  int num_classes, int op, double radius, const double* spacing /* host [3] */, unsigned char* out, void* ws,
                  aide_stream_t stream);
 
+/* ---- resampling: a volume of logical shape (d0, d1, d2) onto the grid (e0, e1, e2) over the same physical extent (the
+ * definition: aide_amd/resample.py).  Per axis with n_in, n_out and output index o, in exact integers:
+ *     num = max((2 o + 1) n_in - n_out, 0)   den = 2 n_out   lo = min(num / den, n_in - 1)   hi = min(lo + 1, n_in - 1)
+ *     w1 = fp64(num - lo den) / fp64(den)  (one division)    w0 = 1 - w1
+ * order 1: the eight corners in the order (a, b, c) = 000, 001, .. 111 (axis 0 slowest) with the weight (w_a * w_b) * w_c, every
+ * product and every sum rounded to fp64 on its own (no fused multiply-add), accumulators starting at +0.  order 0: the voxel
+ * at min(((2 o + 1) n_in) / (2 n_out), n_in - 1) per axis.  The largest accumulator is found with a strict > from class 0 on:
+ * the first index wins a tie, and a NaN never displaces an earlier class.
+ * Launches: TWO per call -- the table of (lo, hi, w1) for the e0 + e1 + e2 output indices into ws, then one gather in which
+ * a thread computes four consecutive elements of the output in its memory order and stores them as one word.  No atomic, no
+ * workgroup waits for another, no host read; every workspace word that is read was written by the same call: two calls give
+ * the same bytes.  All three return AIDE_ERR_ARG before any launch for negative dims, more than 2^31 - 1 voxels (times the
+ * batch) on either side, an order outside {0, 1}, and where the output is not empty an empty input, a null ws or one off 16
+ * bytes; an empty output launches nothing. */
+/* workspace (16-byte aligned): (e0 + e1 + e2) entries of 16 bytes; 0 for dims the entry points reject */
+size_t aide_resample3d_ws_bytes(int64_t e0, int64_t e1, int64_t e2);
+/* v as in aide_morph3d (int64 or uint8 through element strides).  num_classes = C in 2 .. 8: acc[c] += w for every corner
+ * whose value is c (a value outside 0 .. C - 1 belongs to no class and its weight is dropped), out = the first index of the
+ * largest acc; order 0: the nearest voxel's value, 0 when it is outside 0 .. C - 1.  num_classes = 0: the same with C = 2 on
+ * (v != 0).  out: uint8, DENSE, its axes in the memory order (oa0, oa1, oa2) = the logical axes from the slowest to the fastest
+ * (0, 1, 2: contiguous [e0][e1][e2]); the threads follow that order, the arithmetic the logical axes, so the values do not
+ * depend on it.  AIDE_ERR_ARG also for v_u8 outside {0, 1}, num_classes outside {0, 2 .. 8}, (oa0, oa1, oa2) not a
+ * permutation of (0, 1, 2), and on an output that is not empty a null v / out, an out off 4 bytes, an int64 v off 8 bytes. */
+int aide_resample3d_labels(const void* v, int v_u8, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1, int64_t s2,
+                           int64_t e0, int64_t e1, int64_t e2, int num_classes, int order, int oa0, int oa1, int oa2,
+                           unsigned char* out, void* ws, aide_stream_t stream);
+/* x: `batch` fp32 volumes xb elements apart, each read through the element strides (s0, s1, s2); out [batch][e0][e1][e2]
+ * fp32, contiguous.  order 1: out = fp32(sum over the corners of w * fp64(x)), rounded once; order 0: the nearest voxel's
+ * bits.  NaN and inf propagate as the arithmetic says (a corner of weight 0 is still multiplied).  AIDE_ERR_ARG also for a
+ * negative batch and on an output that is not empty a null x / out, an x off 4 bytes, an out off 16 bytes. */
+int aide_resample3d_image(const float* x, int64_t batch, int64_t xb, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1,
+                          int64_t s2, int64_t e0, int64_t e1, int64_t e2, int order, float* out, void* ws, aide_stream_t stream);
+/* p: fp32 probabilities of num_classes = C (2 .. 8) classes cs elements apart, each class a volume (d0, d1, d2) read through
+ * (s0, s1, s2): [S][C][H][W] is passed as it lies, with cs = H W and (s0, s1, s2) = (C H W, W, 1).  Order 1 only:
+ * acc[c] = sum over the corners of w * fp64(p[c]); labels [e0][e1][e2] int64 = the first index of the largest acc;
+ * probs_out (or null) [e0][C][e1][e2] fp32 = fp32(acc).  AIDE_ERR_ARG also for num_classes outside 2 .. 8, C e0 e1 e2 >= 2^31,
+ * and on an output that is not empty a null p / labels, a p off 4 bytes, labels or probs_out off 16 bytes. */
+int aide_resample3d_probs(const float* p, int num_classes, int64_t cs, int64_t d0, int64_t d1, int64_t d2, int64_t s0, int64_t s1,
+                          int64_t s2, int64_t e0, int64_t e1, int64_t e2, int64_t* labels, float* probs_out, void* ws,
+                          aide_stream_t stream);
+
 /* ---- the same for all cases of an epoch at once: K ragged cases concatenated as [S_total][H][W] (contiguous; what the
  * label map yields when fed all slices) with a DEVICE table slice_start[K + 1] (int64, non-decreasing, slice_start[0] >= 0,
  * slice_start[K] <= S_total; an entry outside that is clamped so that no access leaves the buffers).  Case k's logical
